@@ -1,8 +1,10 @@
 """Benchmark of the FacialMMT hot path on MI355X (contract: see the task prompt / DESIGN.md section 6).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself as the line below)
+    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: runs the line below as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full   (also every side measurement listed under --full below)
+    python bench.py ... --dump-outputs DIR                 (also the last timed step's outputs as DIR/<name>.npy)
 
 One step = one target-task training step (train.py:54-143) on a synthetic MELD-shaped batch of `--utts` utterances per GPU
 (default BASELINE.json configs[1]: T+A+V, RoBERTa-large, 160-frame face sequence, batch 4, bf16): the uint8 112x112 face crops
@@ -17,7 +19,9 @@ Other BASELINE.json configs (each run prints its own line naming its configs[i])
     --config 3    BERT-large text encoder (src/models.py:75-77), 4 utterances/GPU                 (configs[3], per-GPU leg)
     --config 4    320-frame face sequence, 1 utterance/GPU, 150 auxiliary images per step          (configs[4], per-GPU leg)
 
-Rank 0 prints ONE JSON line: metric utterances/s (whole job), plus
+Rank 0 prints ONE JSON line: metric utterances/s (whole job), `ms_per_step` = wall time of the K timed steps / K.  A plain run
+sets up, warms up, times the K steps, writes --dump-outputs and prints the line; the fields below that need runs of their own are
+null there and filled in only with --full:
   roofline     -- the dominant kernel family (largest total GPU time among the bracketed many-token launches), timed with HIP
                   events on the launch stream in eager steps issued right after the timed region (the timed steps themselves
                   are HIP-graph replays, inside which nothing can be bracketed).  Its bound follows from its algorithmic
@@ -26,7 +30,13 @@ Rank 0 prints ONE JSON line: metric utterances/s (whole job), plus
                   PMC pass (profiles/traffic.json); `families` lists every bracketed family, `roofline_mfma` / `roofline_hbm`
                   the largest family on either side of the ridge;
   cpu_baseline -- the oracle (CPU restatement, fp32) timed on the host cores of this box on a bounded sample of the same
-                  workload (N=1 only): forward+backward (value) and forward-only, with a thread sweep."""
+                  workload (N=1 only): forward+backward (value) and forward-only, with a thread sweep;
+  pcie_inclusive, other_configs, discarded_swin_gradients_skipped, config.host_issue_ms_into_idle_queue, config.exchange's
+                  exchange-alone figures -- side legs after the timed region (each described where it is measured).
+
+--dump-outputs DIR (rank 0): the step's return values of the LAST timed step (loss, kept-frame mask) and a fixed seeded sample of
+each model's state_dict after it (what the step's caller holds: the trained parameters and buffers), float32 .npy files, < 64 MB.
+Inputs, initial weights and dropout streams are seeded, so two builds run with the same arguments can be compared file by file."""
 from __future__ import annotations
 
 import argparse
@@ -80,7 +90,7 @@ def parse():
     ap.add_argument("--utts", type=int, default=4, help="utterances per GPU per step (BASELINE configs[1]: 4)")
     ap.add_argument("--frames", type=int, default=160, help="face frames per utterance (vision_max_utt_len)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--config", type=int, default=1, choices=[1, 3, 4], help="BASELINE.json configs[i] per-GPU leg: 1 (default), 3 = BERT-large, 4 = 320 frames + auxiliary task")
     ap.add_argument("--plm", default=None, choices=["roberta-large", "bert-large"], help="text encoder architecture (random init)")
     ap.add_argument("--aux-images", type=int, default=None, help="auxiliary-task images per GPU per step (0 = no auxiliary step)")
@@ -90,7 +100,7 @@ def parse():
     ap.add_argument("--overlap-text", type=int, default=1, help="text encoder on a second HIP stream / graph branch, concurrently with Swin")
     ap.add_argument("--plm-dtype", default="bf16", choices=["bf16", "fp32"], help="parameter dtype of the text encoder in --graphs 2: bf16 with fp32 master weights in the optimizer, or fp32 under autocast")
     ap.add_argument("--grad-comm", default="bf16", choices=["fp32", "bf16"], help="element type of the gradient all-reduce (N > 1): bf16 halves the bytes on the xGMI links (0.87 GB instead of 1.74 GB per step)")
-    ap.add_argument("--other-configs", type=int, default=1, help="N = 1 only: after the timed region also run 4 steps of configs[3] and configs[4] (per-GPU legs, own processes) and report them under `other_configs`")
+    ap.add_argument("--other-configs", type=int, default=1, help="--full, N = 1 only: after the timed region also run 4 steps of configs[3] and configs[4] (per-GPU legs, own processes) and report them under `other_configs`")
     ap.add_argument("--branch-graphs", type=int, default=0, help="1 (one rank, --graphs 2, no gradient exchange): text encoder forward / backward and Swin forward / backward as graphs of their own on two streams, events at the data dependencies (GraphedTargetStep branch_graphs)")
     ap.add_argument("--fork-streams", type=int, default=0, help="1 (one rank, --graphs 2, no gradient exchange): one graph whose fork node's first child is a tick on the launch queue, text encoder and Swin each on a stream of their own, forward and backward (GraphedTargetStep fork_streams)")
     ap.add_argument("--pipeline-swin", type=int, default=0, help="1 (one rank, --graphs 2, no auxiliary task): Swin's forward of step i + 1 as a graph of its own, replayed on a second stream beside step i (GraphedTargetStep pipeline_swin); every timed step still runs exactly one Swin forward.  Round 5, same call, alternating: 63.2 / 63.3 ms per step with it, 62.35 / 62.37 without -- the chip-filling Swin kernels (one persistent workgroup per CU) leave the other stream's small launches no CU to run on, so the two graphs time-slice; default off")
@@ -106,11 +116,18 @@ def parse():
                          "the values in force are printed in config.exchange.rccl_env.  Never measured on hardware (no multi-GPU lease): default off")
     ap.add_argument("--swin-cut", type=int, default=-1, help="N > 1: Swin stage behind which the backward graph is cut (-1: chosen from the exchange time measured alone before capture)")
     ap.add_argument("--force-ddp", action="store_true", help="run the data-parallel gradient exchange path even with one process (exercises the N>1 code path on one GPU)")
-    ap.add_argument("--shape-report", default=None, help="write a per-GEMM-shape timing table to this file (development aid)")
-    ap.add_argument("--host-input-leg", type=int, default=1, help="after the timed region, also time the steps with the batch handed over in pinned host memory (PCIe-inclusive rate; reported, never `value`)")
+    ap.add_argument("--shape-report", default=None, help="write a per-GEMM-shape timing table to this file (development aid; implies --full)")
+    ap.add_argument("--host-input-leg", type=int, default=1, help="--full: after the timed region, also time the steps with the batch handed over in pinned host memory (PCIe-inclusive rate; reported, never `value`)")
     ap.add_argument("--cpu-frames", type=int, default=8, help="frames in the CPU-baseline Swin sample")
     ap.add_argument("--rendezvous-check", action="store_true", help="only bring up the process group (one all-reduce of ones), have rank 0 print {\"rendezvous_check\": ..., \"ranks_seen\": N} and exit -- needs no GPU with FMMT_BENCH_BACKEND=gloo; what tests/test_host_cpu.py uses to run `python bench.py --gpus 2` as typed")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run every side measurement (roofline probe passes, CPU baseline, pinned-host-input leg, "
+                                                         "configs[3] / configs[4] and discarded-gradient legs, idle-queue issue time, exchange alone); off: the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs (loss, kept-frame mask, seeded samples of both models' state after the "
+                                                                        "step) as DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    a.full = a.full or bool(a.shape_report)                # the per-shape table is filled by the roofline probe passes
     if a.config == 3:
         a.plm = a.plm or "bert-large"
     if a.config == 4:
@@ -588,7 +605,7 @@ def cpu_baseline(args, cfg):
 
 
 def spawn_command(argv, gpus, port=None):
-    """`python bench.py --gpus N` typed without a launcher (WORLD_SIZE unset, N > 1): the command this process re-executes itself as --
+    """`python bench.py --gpus N` typed without a launcher (WORLD_SIZE unset, N > 1): the command this process runs as its child --
     one rank per GPU under torch.distributed.run on 127.0.0.1 (the container's hostname may not resolve), the same line the driver uses"""
     port = port or int(os.environ.get("FMMT_BENCH_PORT", "0")) or 29500 + os.getpid() % 2000
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
@@ -615,8 +632,10 @@ def rendezvous_check(args, world, rank, backend):
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # typed as `python bench.py --gpus N`: become the launcher (round-5 VERDICT item 6: this used to die on the assertion below)
-        os.execv(sys.executable, spawn_command(sys.argv[1:], args.gpus))
+        # typed as `python bench.py --gpus N`: run the launcher as a child and pass its exit status on (round-5 VERDICT item 6: this used
+        # to die on the assertion below)
+        import subprocess
+        sys.exit(subprocess.call(spawn_command(sys.argv[1:], args.gpus)))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -784,30 +803,35 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # what the last timed step handed its caller, before anything below runs the step again (the graphed step's outputs are static buffers)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, kept, {"swin": swin, "multimodal": mm})
 
     # N > 1: how long the gradient exchange took and how much of it the step could not hide behind Swin's backward (events of the
-    # LAST timed step), and the bus rate of the exchange alone (two blocking exchanges of the same buckets after the timed region)
+    # LAST timed step), and (--full) the bus rate of the exchange alone (two blocking exchanges of the same buckets after the timed region)
     xchg = None
     if ddp and args.graphs == 2:
         total_ms, exposed_ms = step.exchange_ms()
         nbytes = sum(b[0].numel() for b in flat.buckets) * (2 if comm is not None else 4)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t3 = time.perf_counter()
-        for _ in range(2):
-            flat.exchange_all()
-        torch.cuda.synchronize()
-        alone_ms = (time.perf_counter() - t3) / 2 * 1e3
-        flat.zero_grad()
+        alone_ms = None
+        if args.full:
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t3 = time.perf_counter()
+            for _ in range(2):
+                flat.exchange_all()
+            torch.cuda.synchronize()
+            alone_ms = (time.perf_counter() - t3) / 2 * 1e3
+            flat.zero_grad()
         xchg = {"ranks": dist.get_world_size(), "backend": dist.get_backend(), "wire_dtype": args.grad_comm, "bytes_per_rank": nbytes,
                 "buckets": len(flat.buckets), "ms_issue_to_done": round(total_ms, 3), "ms_exposed_after_swin_backward": round(exposed_ms, 3),
-                "ms_alone": round(alone_ms, 3), "ms_alone_before_capture": (round(cut_ms, 3) if cut_ms is not None else None),
+                "ms_alone": (round(alone_ms, 3) if alone_ms is not None else None), "ms_alone_before_capture": (round(cut_ms, 3) if cut_ms is not None else None),
                 "swin_cut": step.SWIN_CUT, "swin_cut_from": ("--swin-cut" if args.swin_cut >= 0 else "exchange measured alone before capture against Swin's backward pieces timed on this device (train_step.pick_swin_cut, measure_swin_tail_ms)"),
                 "swin_tail_ms": tail_ms if (ddp and flat.active and args.swin_cut < 0) else None,
                 "rccl_tuning": args.rccl_tuning, "rccl_env": {k: os.environ.get(k) for k in RCCL_KNOBS},
-                "bus_GB_per_s_alone": round(2.0 * (world - 1) / max(world, 1) * nbytes / (alone_ms * 1e-3) / 1e9, 1) if world > 1 else None}
-        if args.aux_images and aux_step is not None and getattr(aflat, "active", False):
+                "bus_GB_per_s_alone": round(2.0 * (world - 1) / max(world, 1) * nbytes / (alone_ms * 1e-3) / 1e9, 1) if (world > 1 and alone_ms is not None) else None}
+        if args.full and args.aux_images and aux_step is not None and getattr(aflat, "active", False):
             # the auxiliary-task step's own exchange (train.py:15-41: the Swin model's 46.8 M gradients, every `aux_every` target steps): alone, and the
             # whole auxiliary step (graph replays) after the timed region -- not part of `value`
             abytes = sum(b[0].numel() for b in aflat.buckets) * (2 if comm is not None else 4)
@@ -834,20 +858,22 @@ def main():
                                 "aux_images": args.aux_images,
                                 "bus_GB_per_s_alone": round(2.0 * (world - 1) / max(world, 1) * abytes / (a_alone * 1e-3) / 1e9, 1) if world > 1 else None}
 
-    # host cost of issuing one step into an IDLE queue (during the timed loop the host mostly waits for the previous replay
+    # (--full) host cost of issuing one step into an IDLE queue (during the timed loop the host mostly waits for the previous replay
     # of the same graph to drain, so the enqueue time above is back-pressure, not cost)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    one_step()
-    idle_issue_ms = (time.perf_counter() - t1) * 1e3
-    torch.cuda.synchronize()
+    idle_issue_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        one_step()
+        idle_issue_ms = (time.perf_counter() - t1) * 1e3
+        torch.cuda.synchronize()
 
-    # After the timed region (not part of `value`): the same steps with every batch tensor handed over in PINNED HOST memory, as
+    # After the timed region (--full, not part of `value`): the same steps with every batch tensor handed over in PINNED HOST memory, as
     # the reference's DataLoader does (train.py:290-314: `.to(device)` per tensor) -- the step's own copy into its static input
     # tensors then crosses PCIe.  N = 1 only, like the CPU baseline: a reported side figure has no business adding collectives
     # to the N > 1 runs.
     pcie = None
-    if args.graphs == 2 and args.host_input_leg and world == 1:
+    if args.full and args.graphs == 2 and args.host_input_leg and world == 1:
         try:
             pin = lambda ts: tuple(t.detach().cpu().pin_memory() if torch.is_tensor(t) else t for t in ts)
             hb, hab = pin(batch), (pin(aux_batch) if aux_batch is not None else None)
@@ -873,12 +899,12 @@ def main():
         except Exception as e:                               # a reported leg only: never takes the line down
             pcie = {"error": f"{type(e).__name__}: {e}"}
 
-    # After the timed region (not part of `value`): the kernels of the Linear layers bracketed with HIP events in EAGER
+    # After the timed region (--full, not part of `value`): the kernels of the Linear layers bracketed with HIP events in EAGER
     # forward+backward passes on the main stream (inside a graph replay nothing can be bracketed; with --graphs 1 the timed
     # steps themselves are bracketed too, but there the text-encoder graph shares the CUs and stretches every Swin kernel).
     timed_events, timer.events = timer.events, []
-    iso = None
-    if rank == 0:
+    iso = coverage = None
+    if args.full and rank == 0:
         probe_cfg = default_args(get_vision_utt_max_lens=args.frames, trg_accumulation_steps=1 << 30)     # never reaches clip / optimizer
         side, mm.text_stream = getattr(mm, "text_stream", None), None
         probe = TargetStep(swin, mm, None, None, probe_cfg, autocast_dtype=act)
@@ -909,7 +935,7 @@ def main():
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         value = args.utts * world * args.steps / elapsed
-        fams = iso or timer.summary()
+        fams = (iso or timer.summary()) if args.full else None      # a plain run brackets nothing outside the timed steps
         if args.shape_report:
             with open(args.shape_report, "w") as f:
                 f.write(timer.shape_report(args.steps) + "\n")
@@ -999,7 +1025,7 @@ def main():
                        "global_batch": args.utts * world, "frames_per_step_per_gpu": args.utts * args.frames, "aux_images_per_step_per_gpu": args.aux_images,
                        "parallelism": f"dp{world}", "kept_frame_fraction": round(float(kept.mean().item()), 3),
                        "model_tflops_per_s_per_gpu": round(flops_step / (ms * 1e-3) / 1e12, 1),
-                       "host_enqueue_ms_per_step": round(issue_s / args.steps * 1e3, 1), "host_issue_ms_into_idle_queue": round(idle_issue_ms, 1),
+                       "host_enqueue_ms_per_step": round(issue_s / args.steps * 1e3, 1), "host_issue_ms_into_idle_queue": (round(idle_issue_ms, 1) if idle_issue_ms is not None else None),
                        "hip_graphs": {2: ("whole step: 3 graphs (fwd + multimodal bwd | Swin bwd | clip+optimizer), gradient exchange beside the second" if ddp else ("whole step: 3 graphs (Swin fwd of the NEXT step on a second stream | everything else of this step | clip+optimizer)" if getattr(step, "pipeline", False) else ("whole step: 6 graphs on two streams (text fwd || Swin fwd -> filter + fusion + loss fwd/bwd -> text bwd + hand-over + clip+optimizer || Swin bwd)" if getattr(step, "branches", False) else "whole step: 2 graphs (fwd+bwd | clip+optimizer)"))), 1: "multimodal model only (Swin eager)", 0: "none"}[args.graphs],
                        "text_encoder_concurrent_with_swin": bool(args.graphs and args.overlap_text),
                        "swin_forward_pipelined_across_steps": bool(getattr(step, "pipeline", False)),
@@ -1020,11 +1046,11 @@ def main():
             line["config"]["main_stream_gpu_ms_per_phase"] = {k: round(v / args.steps, 1) for k, v in gpu_phase.items()}
         if "FMMT_BENCH_DEVICE" in os.environ or backend != "nccl":
             line["config"]["dry_run"] = f"ranks share device {local}, backend {backend}: not a measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, cfg)
         if args.discarded_swin_gradients == "skip":
             line["config"]["workload"] += "; Swin's (discarded) target-step gradients NOT computed: not the reference's work per step, not comparable with `value` of the default run"
-        if world == 1 and args.other_configs and args.config == 1 and args.discarded_swin_gradients == "compute":
+        if args.full and world == 1 and args.other_configs and args.config == 1 and args.discarded_swin_gradients == "compute":
             line["other_configs"] = other_configs(args)
             line["discarded_swin_gradients_skipped"] = skip_leg(args)
     if dist.is_initialized():
@@ -1038,6 +1064,26 @@ def main():
         except OSError:
             pass
         print(json.dumps(line), flush=True)
+
+
+DUMP_SAMPLE = 1 << 21                # --dump-outputs: positions sampled from each model's state (8 MB of float32 per model)
+
+
+def dump_outputs(out_dir, loss, kept, models):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files.  The step returns (loss, kept-frame mask); what it
+    leaves its caller besides is each model's state after the update: of its floating-point state_dict entries (key order, flattened
+    and concatenated) DUMP_SAMPLE positions drawn by a seeded generator, so every run with the same arguments samples the same ones."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"loss": loss.detach().float().reshape(-1), "kept_mask": kept.detach().float()}
+    for name, model in models.items():
+        flat = torch.cat([t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()])
+        idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(4321)).sort().values
+        arrays[f"{name}_state_sample"] = flat[idx.to(flat.device)]
+        del flat
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy().astype(np.float32))
 
 
 def bracket_coverage(timer, one_pass, pass_ms):
@@ -1077,11 +1123,11 @@ def bracket_coverage(timer, one_pass, pass_ms):
 
 def other_configs(args):
     """BASELINE.json configs[3] (BERT-large) and configs[4] (320 frames + auxiliary task): per-GPU legs, 4 timed steps each, each in
-    its own process (own models, own graphs) after this one's timed region -- reported, never part of `value`."""
+    its own process (own models, own graphs; --full for the roofline fields) after this one's timed region -- reported, never part of `value`."""
     import subprocess
     out = {}
     for c in (3, 4):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--host-input-leg", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(c), "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--host-input-leg", "0",
                "--other-configs", "0", "--dtype", args.dtype, "--graphs", str(args.graphs)]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
@@ -1098,7 +1144,8 @@ def other_configs(args):
 def skip_leg(args):
     """The same configs[1] step with train_step's discarded_swin_gradients="skip" (own process, 6 steps): a REPORTED leg -- the
     reference spends this backward on gradients it zeroes unread; skipping it leaves every later parameter unchanged to fp32 rounding
-    (tests/test_gpu_train_step.py::test_skipping_the_discarded_swin_backward_changes_nothing).  Never `value`."""
+    (tests/test_gpu_train_step.py::test_skipping_the_discarded_swin_backward_changes_nothing).  Never `value`.  Only the child's timed steps
+    are read, so the child is a plain run."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--host-input-leg", "0", "--other-configs", "0",
            "--dtype", args.dtype, "--graphs", str(args.graphs), "--discarded-swin-gradients", "skip"]

@@ -11,21 +11,21 @@ O=$R/gpurun_out
 S=$O/summ_$TAG
 mkdir -p $O $S
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout 900 python $R/bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 tail -1 $O/bench_$TAG.json > $S/bench.json
 for c in 3 4; do
-  timeout 600 python $R/bench.py --config $c --no-cpu-baseline 2> $O/bench_c${c}_$TAG.err | tail -1 > $S/bench_config$c.json
+  timeout 600 python $R/bench.py --full --config $c --no-cpu-baseline 2> $O/bench_c${c}_$TAG.err | tail -1 > $S/bench_config$c.json
 done
-# per-kernel GPU time of the default command minus the CPU leg: 2 eager warm-up passes inside the graph capture + 2 warm-up
+# per-kernel GPU time of the --full command minus the CPU leg: 2 eager warm-up passes inside the graph capture + 2 warm-up
 # + 6 timed + 1 idle-queue step (all graph replays) + 3 eager probe passes = 14 passes
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o r --output-format csv -- python $R/bench.py --no-cpu-baseline --host-input-leg 0 > $O/prof_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o r --output-format csv -- python $R/bench.py --full --no-cpu-baseline --host-input-leg 0 > $O/prof_$TAG.log 2>&1
 # the same without the text branch forked onto its own stream: per-kernel durations undisturbed by concurrent text-encoder work
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/profiso_$TAG -o r --output-format csv -- python $R/bench.py --no-cpu-baseline --host-input-leg 0 --overlap-text 0 > $O/profiso_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/profiso_$TAG -o r --output-format csv -- python $R/bench.py --full --no-cpu-baseline --host-input-leg 0 --overlap-text 0 > $O/profiso_$TAG.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_${c}_$TAG -o r --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graphs 0 > $O/pmc_${c}_$TAG.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc $c -d $O/pmc_${c}_$TAG -o r --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --graphs 0 > $O/pmc_${c}_$TAG.log 2>&1
 done
-timeout 400 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_MFMA_$TAG -o r --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graphs 0 > $O/pmc_MFMA_$TAG.log 2>&1
-timeout 400 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVE_CYCLES -d $O/pmc_LDS_$TAG -o r --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graphs 0 > $O/pmc_LDS_$TAG.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_MFMA_$TAG -o r --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --graphs 0 > $O/pmc_MFMA_$TAG.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVE_CYCLES -d $O/pmc_LDS_$TAG -o r --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --graphs 0 > $O/pmc_LDS_$TAG.log 2>&1
 # summarise on the box and drop the raw traces (gpurun copies back at most 64 MiB)
 cd $R
 PROF_ROWS=60 python tools/summarize_prof.py stats $O/prof_$TAG 14 > $S/kernel_stats.md
