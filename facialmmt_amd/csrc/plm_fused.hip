@@ -333,6 +333,10 @@ int gb_blocks(int M) { const int b = (M + GB_PH - 1) / GB_PH; return b < GB_BLOC
 //     colsum_kernel), every row written.
 // C % 8 == 0, C <= 2048; dy bf16 [T][C]; ids int64 [T].
 constexpr int EB_SMALL = 8;
+constexpr int EB_MAX_T = 32768;
+constexpr int eb_lds_bytes(int T) { return (T + 31) / 32 * 4 + T * 4; }
+constexpr int EB_LDS_MAX = eb_lds_bytes(EB_MAX_T);
+static_assert(EB_LDS_MAX <= 160 * 1024, "embedding_bwd_kernel: the largest T must fit a gfx950 workgroup's LDS");
 __global__ __launch_bounds__(256) void embedding_bwd_kernel(int T, int C, const long long* __restrict__ ids, long long padding_idx, const bf16* __restrict__ dy,
                                                            bf16* __restrict__ dw) {
     extern __shared__ unsigned eb_lds[];                    // [nwords] bitmap, then the ordered list of the duplicates (T ints)
@@ -510,7 +514,7 @@ extern "C" int fmmt_plm_gelu_bwd_colsum(int M, int H, const void* dact, const vo
 }
 
 extern "C" int fmmt_embedding_bwd(int T, int C, int V, const int64_t* ids, int64_t padding_idx, const void* dy, void* dweight, void* stream) {
-    if (T <= 0 || C <= 0 || V <= 0 || C % 8 || C > 2048 || T > 32768 || !ids || !dy || !dweight) return FMMT_EINVAL;
+    if (T <= 0 || C <= 0 || V <= 0 || C % 8 || C > 2048 || T > EB_MAX_T || !ids || !dy || !dweight) return FMMT_EINVAL;
     if (pf_misaligned(dy, dweight, dy, dweight)) return FMMT_EALIGN;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (V <= EB_SMALL) {
@@ -519,8 +523,11 @@ extern "C" int fmmt_embedding_bwd(int T, int C, int V, const int64_t* ids, int64
         FMMT_CHECK_LAUNCH();
         return 0;
     }
+    // the bitmap + list pass 64 KiB at T = 15888: the limit is raised once per device to the need of the largest T taken (32768: 135168 B of the 160 KiB)
+    static FmmtLdsOnce lds_once;
+    if (int e = lds_once.set(reinterpret_cast<const void*>(embedding_bwd_kernel), EB_LDS_MAX)) return e;
     if (hipError_t e = hipMemsetAsync(dweight, 0, (size_t)V * C * sizeof(bf16), st); e != hipSuccess) return (int)e;
-    const size_t lds = (size_t)((T + 31) / 32) * 4 + (size_t)T * 4;
+    const size_t lds = eb_lds_bytes(T);
     hipLaunchKernelGGL(embedding_bwd_kernel, dim3(T), dim3(256), lds, st, T, C, (const long long*)ids, (long long)padding_idx, (const bf16*)dy, (bf16*)dweight);
     FMMT_CHECK_LAUNCH();
     return 0;

@@ -583,6 +583,9 @@ class PlmSelfAttnFn(torch.autograd.Function):
         qkv = torch.nn.functional.linear(x, w_all, b_all)
         seed_t = seed if isinstance(seed, torch.Tensor) else None
         seed_i = 0 if seed_t is not None else int(seed)
+        if key_bias is not None:                                 # the kernels read it as a row-major fp32 (B, S) array
+            key_bias = key_bias.detach().to(torch.float32).contiguous()
+            assert key_bias.shape == x.shape[:2], f"key_bias must be (B, S) = {tuple(x.shape[:2])}, got {tuple(key_bias.shape)}"
         out, lse = mha_packed_bm_fwd_raw(qkv, int(num_heads), float(scale), float(p), seed_i, seed_t, key_bias)
         ctx.save_for_backward(x, w_all, qkv, out, lse, seed_t, key_bias)
         ctx.cfg = (int(num_heads), float(scale), float(p), seed_i)

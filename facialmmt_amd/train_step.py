@@ -384,10 +384,28 @@ class _SeedBox:
     def __init__(self):
         self.t = None
         self.words = 1            # word 0: the sublayer tails (each adds its salt); word 1 + i: attention module i (its kernels take no salt)
-        self.key_bias = None      # (the 4-d mask the layers were handed, its version counter, its per-key logit bias): _fused_attention
+        # the attention mask the caller handed the encoder, recorded by its pre-hook for the length of one forward: (mask: None or (batch, keys)
+        # padding mask, its per-key logit bias once _fused_attention made it), or None = no forward of the encoder in progress or a mask of another
+        # form (per query, causal, packed sequences ...): the layers' 4-d mask cannot tell a padding mask from those, so only this record decides.
+        # A layer forward re-run after the model's forward returned (activation-checkpoint recomputation in the backward) finds no record and
+        # would take the stock attention where the original forward took the fused one: a model with gradient checkpointing on records nothing
+        self.mask = None
 
     def draw(self, device):
         self.t = torch.randint(0, 2 ** 62, (self.words,), dtype=torch.int64, device=device)
+
+    def pre_hook(self, mod, args, kwargs):
+        """forward pre-hook of the encoder: the seed word draw (training) and the record of the caller's attention mask (keyword or second positional)"""
+        if mod.training:
+            self.draw(next(mod.parameters()).device)
+        mask = kwargs["attention_mask"] if "attention_mask" in kwargs else (args[1] if len(args) > 1 else None)
+        if getattr(mod, "is_gradient_checkpointing", False):
+            self.mask = None
+        else:
+            self.mask = [None, None] if mask is None else ([mask, None] if torch.is_tensor(mask) and mask.dim() == 2 else None)
+
+    def post_hook(self, mod, args, kwargs, out):
+        self.mask = None
 
 
 def _sublayer_tail_forward(self, hidden_states, input_tensor):
@@ -405,8 +423,12 @@ def _sublayer_tail_forward(self, hidden_states, input_tensor):
 
 
 def _fused_ffn_chunk(self, attention_output):
-    """feed_forward_chunk of a re-classed transformers *Layer: intermediate + output as one autograd node (ops.PlmFfnFn), or the stock pair of modules"""
+    """feed_forward_chunk of a re-classed transformers *Layer: intermediate + output as one autograd node (ops.PlmFfnFn), or the stock pair of modules.
+    A layer whose feed-forward runs in sequence chunks (config.chunk_size_feed_forward) takes the stock modules' own forwards: the fused dropout stream
+    counts rows from 0 in every call with the module's one salt, so every chunk would draw the same mask."""
     inter, out = self.intermediate, self.output
+    if getattr(self, "chunk_size_feed_forward", 0):
+        return out._fmmt_stock_forward(inter(attention_output), attention_output)
     d1, d2, ln = inter.dense, out.dense, out.LayerNorm
     p = float(out.dropout.p) if self.training else 0.0
     box = out._fmmt_seed
@@ -468,9 +490,10 @@ def _packed_qkv_forward(self, hidden_states, *args, **kwargs):
 
 def _fused_attention(self, hidden_states, args, kwargs, w, b):
     """the attention core of a packed *SelfAttention on the in-tree kernels (ops.PlmSelfAttnFn), or None where they do not apply (then: the stock attention
-    interface behind the packed projection).  Encoder self-attention only: bf16, head_dim 64, no cache, no head mask, no attention weights asked for; the
-    mask transformers hands down -- None, or the 4-d form of a (batch, keys) padding mask, boolean (sdpa) or additive (eager), whose rows are all alike for a
-    bidirectional encoder -- becomes the kernels' per-key logit bias from its first query row."""
+    interface behind the packed projection).  Encoder self-attention only: bf16, head_dim 64, no cache, no head mask, no attention weights asked for, and
+    only inside a forward of the encoder whose caller passed no mask or a (batch, keys) padding mask (_SeedBox.pre_hook): that mask becomes the kernels'
+    per-key logit bias.  transformers hands the layers the 4-d form of any mask, and a padding mask's is contiguous (B, 1, S, S) like a per-query one's
+    (sequence packing, causal): a 4-d mask from the caller takes the stock interface."""
     if not PLM_FUSE_ATTN or hidden_states.dim() != 3 or hidden_states.dtype != torch.bfloat16:
         return None
     nH = int(getattr(self, "num_attention_heads", 0))
@@ -483,20 +506,22 @@ def _fused_attention(self, hidden_states, args, kwargs, w, b):
         return None
     mask = args[0] if args else kwargs.get("attention_mask")
     B, S, _ = hidden_states.shape
-    key_bias = None
-    if mask is not None:
-        if not torch.is_tensor(mask) or mask.dim() != 4 or mask.shape[0] != B or mask.shape[1] != 1 or mask.shape[-1] != S or mask.shape[2] not in (1, S):
-            return None
-        # once per forward of the encoder, not once per layer: every layer is handed the same mask tensor (the box keeps it, so its identity cannot recur)
-        cached = getattr(self._fmmt_seed, "key_bias", None)
-        if cached is not None and cached[0] is mask and cached[1] == mask._version:
-            key_bias = cached[2]
-        else:
-            row = mask[:, 0, 0, :]
-            key_bias = (torch.where(row, 0.0, -30000.0) if row.dtype == torch.bool else row.float().clamp_min(-30000.0)).to(torch.float32).contiguous()
-            self._fmmt_seed.key_bias = (mask, mask._version, key_bias)
-    p = float(self.dropout.p) if self.training else 0.0
     box = getattr(self, "_fmmt_seed", None)
+    rec = box.mask if box is not None else None
+    if rec is None:
+        return None
+    if mask is not None and (not torch.is_tensor(mask) or mask.dim() != 4 or mask.shape[0] != B or mask.shape[1] != 1 or mask.shape[-1] != S
+                             or mask.shape[2] not in (1, S)):
+        return None
+    key_bias = None
+    if rec[0] is not None:
+        if rec[0].shape != (B, S):
+            return None
+        if rec[1] is None:                                  # once per forward of the encoder, not once per layer
+            m2 = rec[0] if rec[0].dtype == torch.bool else rec[0] != 0
+            rec[1] = torch.where(m2, 0.0, -30000.0).to(torch.float32).contiguous()     # the kernels read it row-major: a transposed mask keeps its strides
+        key_bias = rec[1]
+    p = float(self.dropout.p) if self.training else 0.0
     if p > 0.0 and (box is None or box.t is None or box.t.numel() <= self._fmmt_attn_word):
         return None
     seed = box.t[self._fmmt_attn_word:self._fmmt_attn_word + 1] if p > 0.0 else 0
@@ -579,7 +604,8 @@ def fuse_text_encoder(plm, tails: bool = True, qkv: bool = True):
             m._fmmt_stock_forward = m.forward
             m.forward = types.MethodType(_fused_embedding_forward, m)
     if n_tail or n_qkv:
-        plm.register_forward_pre_hook(lambda mod, args, kwargs=None: box.draw(next(mod.parameters()).device) if mod.training else None)
+        plm.register_forward_pre_hook(box.pre_hook, with_kwargs=True)
+        plm.register_forward_hook(box.post_hook, with_kwargs=True, always_call=True)
     return n_tail, n_qkv
 
 
