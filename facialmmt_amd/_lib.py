@@ -80,6 +80,8 @@ SIGNATURES = {
     "fmmt_patch_embed_u8": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "fmmt_patch_embed_ln_fwd": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p]),
     "fmmt_patch_embed_u8_ln_fwd": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
+    "fmmt_emotion_head_fwd": (_i, [_i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p]),
+    "fmmt_eval_accumulate": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, C.c_int64, C.c_int64, _p]),
 }
 
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3

@@ -1697,3 +1697,83 @@ class PosEmbScaleFn(Function):
 
 def posemb_scale(x, table, scale):
     return PosEmbScaleFn.apply(x, table, float(scale))
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation (csrc/eval.hip): forward only
+# ------------------------------------------------------------------------------------------------
+def _no_grad_only(what, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise NotImplementedError(f"{what} is forward only (evaluation): call it under torch.no_grad() or on detached tensors")
+
+
+def emotion_head_raw(feats, w1, b1, w2, b2, tau, gumbel=None):
+    """fmmt_emotion_head_fwd on tensors: feats (N, K) bf16 / fp32 (any row stride that is a multiple of 4), w1 (64, K), b1 (64,), w2 (NL, 64),
+    b2 (NL,) fp32, gumbel (N, NL) fp32 or None.  Returns (preds (N, NL) fp32, importance (N,) fp32)."""
+    _need_cuda(feats, "emotion_head")
+    _no_grad_only("emotion_head", feats, w1, b1, w2, b2, gumbel)
+    if feats.dim() != 2 or w1.dim() != 2 or w2.dim() != 2:
+        raise _lib.FmmtError("emotion_head: feats (N, K), w1 (H, K), w2 (NL, H)")
+    N, K = feats.shape
+    H, NL = w1.shape[0], w2.shape[0]
+    if w1.shape[1] != K or w2.shape[1] != H or b1.shape != (H,) or b2.shape != (NL,):
+        raise _lib.FmmtError(f"emotion_head: shapes do not chain: feats {tuple(feats.shape)}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}")
+    f = feats.detach()
+    if f.stride(1) != 1 or f.stride(0) % 4 or f.stride(0) < K or f.data_ptr() % 16:
+        f = _c16(f)
+    ws = [t.detach() for t in (w1, b1, w2, b2)]
+    if any(t.dtype != torch.float32 for t in ws):
+        raise _lib.FmmtError("emotion_head: the head's parameters are read as fp32 (the module's own; no shadow copies)")
+    ws = [t if t.is_contiguous() else t.contiguous() for t in ws]
+    g = None
+    if gumbel is not None:
+        if tuple(gumbel.shape) != (N, NL):
+            raise _lib.FmmtError(f"emotion_head: gumbel must be (N, NL) = ({N}, {NL}), got {tuple(gumbel.shape)}")
+        g = gumbel.detach().float().contiguous()
+    preds = torch.empty((N, NL), dtype=torch.float32, device=f.device)
+    imp = torch.empty((N,), dtype=torch.float32, device=f.device)
+    if N == 0:
+        return preds, imp
+    check(_lib.load().fmmt_emotion_head_fwd(dtype_code(f.dtype), N, K, H, NL, _p(f), f.stride(0), _p(ws[0]), _p(ws[1]), _p(ws[2]), _p(ws[3]), _p(g), float(tau),
+                                            _p(preds), _p(imp), _st()), f"fmmt_emotion_head_fwd(N={N},K={K},H={H},NL={NL})")
+    return preds, imp
+
+
+def emotion_head(feats, linear, classifier, tau, gumbel=None):
+    """The target-task head of SwinForAffwildClassification at inference (src/models.py:28-32) and the importance score of train.py:186-188 as one
+    launch: `linear` / `classifier` are the module's two nn.Linear layers, `gumbel` the noise F.gumbel_softmax would add (None: no noise).
+    Returns (preds, importance)."""
+    return emotion_head_raw(feats, linear.weight, linear.bias, classifier.weight, classifier.bias, tau, gumbel)
+
+
+def gumbel_noise(n, num_labels, device, dtype=torch.float32):
+    """the noise of F.gumbel_softmax, drawn exactly as it draws it (one exponential_ over a logits-shaped tensor of the logits' dtype): the same
+    generator state gives the same numbers"""
+    return -torch.empty((n, num_labels), dtype=dtype, device=device).exponential_().log()
+
+
+def eval_accumulate(logits, labels, acc, logits_out=None, out_offset=0, pred=True):
+    """fmmt_eval_accumulate: logits (B, NL) bf16 / fp32, labels (B,) int64 (negative: ignored), acc: int64 CUDA tensor of 2 + NL * NL words --
+    [0] the loss sum (the bits of a double), [1] the row count, [2:] the confusion matrix [label][argmax] -- updated in place; logits_out
+    (capacity, NL) fp32 receives the rows at [out_offset, out_offset + B).  Returns the argmax (B,) int32, or None with pred=False."""
+    _need_cuda(logits, "eval_accumulate")
+    _no_grad_only("eval_accumulate", logits)
+    if logits.dim() != 2 or labels.shape != (logits.shape[0],):
+        raise _lib.FmmtError("eval_accumulate: logits (B, NL), labels (B,)")
+    B, NL = logits.shape
+    if acc.dtype != torch.int64 or acc.numel() != 2 + NL * NL or not acc.is_contiguous() or not acc.is_cuda:
+        raise _lib.FmmtError(f"eval_accumulate: acc must be a contiguous int64 CUDA tensor of {2 + NL * NL} words")
+    lg = logits.detach()
+    if lg.stride(1) != 1:
+        lg = lg.contiguous()
+    lab = labels.detach().to(device=lg.device, dtype=torch.int64).contiguous()
+    cap = 0
+    if logits_out is not None:
+        if logits_out.dtype != torch.float32 or logits_out.dim() != 2 or logits_out.shape[1] != NL or not logits_out.is_contiguous():
+            raise _lib.FmmtError("eval_accumulate: logits_out must be a contiguous fp32 (capacity, NL) tensor")
+        cap = logits_out.shape[0]
+    out = torch.empty((B,), dtype=torch.int32, device=lg.device) if pred else None
+    a = acc.data_ptr()
+    check(_lib.load().fmmt_eval_accumulate(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), a, a + 8, a + 16, _p(out), _p(logits_out), int(out_offset),
+                                           int(cap), _st()), f"fmmt_eval_accumulate(B={B},NL={NL})")
+    return out

@@ -19,6 +19,8 @@ Registered (forward ops return what their backward needs as extra outputs, as cu
     fmmt::posemb_scale(x, table, scale) -> y                                              sqrt(E) x + sinusoidal position embedding
     fmmt::window_block(x, ln_w, ln_b, eps, wqkv, bqkv?, wproj, bproj?, table, index, n_img, H, W, heads, shift, scale, rowscale?)
                        -> (y, xn, attn_out, mean, rstd, lse)                               norm1 -> (S)W-MSA -> proj -> residual (C = 96: one launch; 192: four), recompute backward
+    fmmt::emotion_head(feats, w1, b1, w2, b2, gumbel?, tau) -> (preds, importance)         evaluation: Swin's target-task head + Gumbel-softmax + importance (no gradient)
+    fmmt::eval_accumulate(logits, labels, acc!, logits_out!?, out_offset) -> pred           evaluation: loss sum / count / confusion matrix accumulated on the device (no gradient)
 
 The nn.Modules of facialmmt_amd/modules keep using ops.py (fewer dispatcher hops per launch); tests/test_gpu_torch_ops.py
 holds the two front ends bit-identical, forward and backward, and runs torch.library.opcheck on each operator."""
@@ -510,3 +512,24 @@ def _wb_backward(ctx, dy, *_unused):
 
 
 window_block.register_autograd(_wb_backward, setup_context=_wb_setup)
+
+
+# ------------------------------------------------------------------------------------------------ evaluation (forward only)
+@torch.library.custom_op(f"{_LIB}::emotion_head", mutates_args=(), device_types="cuda")
+def emotion_head(feats: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, gumbel: Optional[Tensor], tau: float) -> Tuple[Tensor, Tensor]:
+    return ops.emotion_head_raw(feats, w1, b1, w2, b2, tau, gumbel)
+
+
+@emotion_head.register_fake
+def _(feats, w1, b1, w2, b2, gumbel, tau):
+    return (feats.new_empty(feats.shape[0], w2.shape[0], dtype=torch.float32), feats.new_empty(feats.shape[0], dtype=torch.float32))
+
+
+@torch.library.custom_op(f"{_LIB}::eval_accumulate", mutates_args=("acc", "logits_out"), device_types="cuda")
+def eval_accumulate(logits: Tensor, labels: Tensor, acc: Tensor, logits_out: Optional[Tensor], out_offset: int) -> Tensor:
+    return ops.eval_accumulate(logits, labels, acc, logits_out, out_offset)
+
+
+@eval_accumulate.register_fake
+def _(logits, labels, acc, logits_out, out_offset):
+    return logits.new_empty(logits.shape[0], dtype=torch.int32)

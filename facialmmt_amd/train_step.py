@@ -360,6 +360,26 @@ PLM_FUSE_ATTN = True                                        # a packed *SelfAtte
 PLM_FUSE_TAILS, PLM_FUSE_QKV = True, True                  # fuse_text_encoder: sublayer tails as one launch per direction / packed query-key-value GEMM
 
 
+class fused_inference:
+    """`with fused_inference():` -- inside it the fused forwards of fuse_text_encoder (sublayer tails, the feed-forward node, the packed
+    query / key / value projection with the in-tree attention core) also run when autograd is off, with p = 0 and nothing kept for a backward.
+    Outside it a `no_grad` caller gets the stock modules, as before: the evaluation steps (eval_step.py) opt in, nobody else is changed."""
+    depth = 0
+
+    def __enter__(self):
+        fused_inference.depth += 1
+        return self
+
+    def __exit__(self, *exc):
+        fused_inference.depth -= 1
+        return False
+
+
+def _fusable_now():
+    """autograd on (training: the fused nodes carry their own backward) or an evaluation step opted in (fused_inference)"""
+    return torch.is_grad_enabled() or fused_inference.depth > 0
+
+
 def use_colsum_bias_gradients(module):
     """Re-class every nn.Linear of `module` (a Hugging Face text encoder) as VendorLinear: the bias gradients of its ~146 Linear
     layers then cost one 4 us launch each instead of a memset + a multi-block reduction (measured: 3.2 + 0.8 ms per step).
@@ -414,7 +434,7 @@ def _sublayer_tail_forward(self, hidden_states, input_tensor):
     p = float(self.dropout.p) if self.training else 0.0
     box = self._fmmt_seed
     if (not hidden_states.is_cuda or hidden_states.dtype != torch.bfloat16 or d.weight.dtype != torch.bfloat16 or ln.weight.dtype != torch.bfloat16
-            or d.bias is None or ln.bias is None or d.weight.shape[0] % 8 or d.weight.shape[0] > 2048 or not torch.is_grad_enabled()
+            or d.bias is None or ln.bias is None or d.weight.shape[0] % 8 or d.weight.shape[0] > 2048 or not _fusable_now()
             or (p > 0.0 and box.t is None)):
         return self._fmmt_stock_forward(hidden_states, input_tensor)
     from . import ops
@@ -433,7 +453,7 @@ def _fused_ffn_chunk(self, attention_output):
     p = float(out.dropout.p) if self.training else 0.0
     box = out._fmmt_seed
     x = attention_output
-    if (not PLM_FUSE_FFN or not x.is_cuda or x.dtype != torch.bfloat16 or not torch.is_grad_enabled() or d1.bias is None or d2.bias is None or ln.bias is None
+    if (not PLM_FUSE_FFN or not x.is_cuda or x.dtype != torch.bfloat16 or not _fusable_now() or d1.bias is None or d2.bias is None or ln.bias is None
             or any(t.dtype != torch.bfloat16 for t in (d1.weight, d2.weight, ln.weight)) or d2.weight.shape[0] % 8 or d2.weight.shape[0] > 2048
             or d1.weight.shape[0] % 8 or d1.weight.shape[0] > 8192 or d1.weight.shape[1] != d2.weight.shape[0] or (p > 0.0 and box.t is None)):
         return self._fmmt_stock_ffn(attention_output)
@@ -466,7 +486,7 @@ def _packed_qkv_forward(self, hidden_states, *args, **kwargs):
     behind the projections (head split, the attention interface, dropout) is the stock method's, fed through three pass-through Linear stand-ins"""
     w, b = self._fmmt_qkv
     q, k, v = self.query, self.key, self.value
-    ok = (hidden_states.is_cuda and hidden_states.dtype == w.dtype and torch.is_grad_enabled() and q.weight.data_ptr() == w.data_ptr()
+    ok = (hidden_states.is_cuda and hidden_states.dtype == w.dtype and _fusable_now() and q.weight.data_ptr() == w.data_ptr()
           and k.weight.data_ptr() == w.data_ptr() + w[0].numel() * w.shape[0] // 3 * w.element_size()
           and v.weight.data_ptr() == w.data_ptr() + 2 * w[0].numel() * w.shape[0] // 3 * w.element_size() and q.bias.data_ptr() == b.data_ptr())
     # key / value from another tensor (cross-attention) or a cache: the packed projection of hidden_states would silently be the wrong one

@@ -488,6 +488,28 @@ int fmmt_patch_embed_u8_ln_fwd(int dtype, int mode, int n_img, int in_size, cons
                                const void* w, const float* bias, const float* ln_gamma, const float* ln_beta, float eps,
                                void* cols, void* x_pre, void* y, float* mean, float* rstd, void* stream);
 
+/* Evaluation (train.py:154-243 multimodal_evaluate, utils/eval_metrics.py:16-28), the two pieces of device work only it has.
+ *
+ * fmmt_emotion_head_fwd: the target-task head of SwinForAffwildClassification at inference (src/models.py:28-32: linear -> ReLU -> classifier ->
+ * F.gumbel_softmax) and the importance score of train.py:186-188 (diag(P P^T)) as ONE launch, forward only:
+ *   feats [N][K] (`dtype`, row stride ld elements) -> Linear(K, H) + b1 -> ReLU -> Linear(H, NL) + b2 -> (+ gumbel[N][NL] if non-NULL) / tau -> softmax
+ *   -> preds [N][NL] fp32, importance [N] fp32 = sum_c preds^2 (or NULL).  All arithmetic fp32 (exact-fp32 MFMA); w1 [H][K], b1 [H], w2 [NL][H],
+ *   b2 [NL] are the module's fp32 parameters read as they are.  The Gumbel noise is an INPUT (-log of unit exponentials, drawn by the caller as
+ *   F.gumbel_softmax draws it); NULL: softmax(logits / tau).  H = 64, K % 64 == 0, NL <= 8, tau > 0, else FMMT_EINVAL; feats / w1 16-byte aligned,
+ *   ld % 4 == 0, else FMMT_EALIGN.
+ * fmmt_eval_accumulate: the per-batch bookkeeping of train.py:231-234 (loss.item(), concatenated logits) and the counts behind
+ * utils/eval_metrics.py:16-28 (f1_score) as ONE launch without a host synchronisation:
+ *   logits [B][NL] (`dtype`, row stride ld), labels [B] int64 (negative: the row is ignored, as torch's ignore_index -- padded rows; a label >= NL is
+ *   skipped the same way) -> per row fp32 log-sum-exp cross entropy and argmax (first maximum, as numpy.argmax);
+ *   *loss_sum (double) += sum of the row losses, *count (int64) += rows not ignored, confusion [NL][NL] int64 += 1 at [label][argmax];
+ *   pred [B] int32 = argmax (or NULL); logits_out (or NULL): fp32 [out_capacity][NL], rows [out_offset, out_offset + B) receive the logits.
+ *   The three accumulators are caller-owned device memory that persists over a split (the caller zeroes them).  One workgroup, the row losses summed
+ *   in double by a fixed tree: two runs give the same bits.  B <= 1024, NL <= 8, out_offset + B <= out_capacity, else FMMT_EINVAL. */
+int fmmt_emotion_head_fwd(int dtype, int N, int K, int H, int NL, const void* feats, int ld, const float* w1, const float* b1, const float* w2,
+                          const float* b2, const float* gumbel, float tau, float* preds, float* importance, void* stream);
+int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, const int64_t* labels, double* loss_sum, int64_t* count,
+                         int64_t* confusion, int32_t* pred, float* logits_out, int64_t out_offset, int64_t out_capacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
