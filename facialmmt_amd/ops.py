@@ -105,7 +105,12 @@ def _lp(w: torch.Tensor, dtype, transpose: bool = False) -> torch.Tensor:
     transposed+contiguous (the input-gradient GEMM wants W^T row-major).  Shadows are cached per parameter OBJECT
     (for a view such as in_proj_weight[a:b]: its base) and version, and dropped when that object dies -- an
     address-based key would hand a new model the shadows of a freed one that happened to occupy the same memory.
-    They are rebuilt only after an optimizer step touched the master copy."""
+    They are rebuilt only after an optimizer step touched the master copy.
+
+    Operands: while a graph is captured outside a pinned_scope (every fp32 step, a bf16 one with PIN_SHADOWS off) the result is a FRESH tensor
+    that nothing else keeps alive.  A caller that hands two of them to one launch must hold both in variables until the launch is enqueued:
+    `_p(_lp(a)), _p(_lp(b))` frees the first before the second is allocated, the allocator gives the second the same block, and the kernel
+    reads b through both pointers (found by tests/test_gpu_step_oracle.py: the captured fp32 auxiliary step's gradients below Swin stage 1)."""
     base = w._base if w._base is not None else w
     wd = w.detach()
     if wd.dtype == dtype and not transpose:
@@ -711,7 +716,8 @@ def mlp_bwd_input_raw(dy2, h_pre, w1, w2, rowscale, rows_per_scale, dg=False):
     if _MLP_BWD_FUSED and _mlp_dtype_ok(dt) and C in _MLP_BWD_WIDTHS and w1.shape == (4 * C, C) and M >= 4096:
         dh = torch.empty((M, 4 * C), dtype=dt, device=dy2.device)
         dx = torch.empty_like(dy2)
-        rc = _lib.load().fmmt_mlp_bwd_input(dtype_code(dt) | (SAVE_DG if dg else 0), M, C, _p(dy2), _p(h_pre), _p(_lp(w2, dt, transpose=True)), _p(_lp(w1, dt, transpose=True)),
+        w2t, w1t = _lp(w2, dt, transpose=True), _lp(w1, dt, transpose=True)     # both alive until the launch is enqueued (_lp's note on operands)
+        rc = _lib.load().fmmt_mlp_bwd_input(dtype_code(dt) | (SAVE_DG if dg else 0), M, C, _p(dy2), _p(h_pre), _p(w2t), _p(w1t),
                                             _p(rowscale), rows_per_scale, _p(dh), _p(dx), _st())
         check(rc, f"fmmt_mlp_bwd_input(M={M},C={C})")
         return dh, dx
@@ -740,8 +746,9 @@ class MlpLnFn(Function):
         h_pre = torch.empty((M, 4 * C), dtype=x.dtype, device=dev) if train else None
         h = torch.empty_like(h_pre) if train else None
         ctx.dg = bool(train and _MLP_SAVE_DG and C in _MLP_FUSED_DG_WIDTHS)
-        rc = _lib.load().fmmt_mlp_ln_fwd(dtype_code(x.dtype) | (SAVE_DG if ctx.dg else 0), M, C, _p(x2), _p(g), _p(b), float(eps), _p(_lp(w1, x.dtype)), _p(b1.detach().float().contiguous()),
-                                         _p(_lp(w2, x.dtype)), _p(b2.detach().float().contiguous()), _p(rowscale), rows_per_scale, _p(y), _p(xn), _p(mean), _p(rstd),
+        w1l, w2l, b1f, b2f = _lp(w1, x.dtype), _lp(w2, x.dtype), b1.detach().float().contiguous(), b2.detach().float().contiguous()
+        rc = _lib.load().fmmt_mlp_ln_fwd(dtype_code(x.dtype) | (SAVE_DG if ctx.dg else 0), M, C, _p(x2), _p(g), _p(b), float(eps), _p(w1l), _p(b1f),
+                                         _p(w2l), _p(b2f), _p(rowscale), rows_per_scale, _p(y), _p(xn), _p(mean), _p(rstd),
                                          _p(h_pre), _p(h), _st())
         check(rc, f"fmmt_mlp_ln_fwd(M={M},C={C})")
         ctx.save_for_backward(x2, xn, mean, rstd, g, w1, w2, h_pre, h, rowscale)
@@ -764,7 +771,8 @@ class MlpLnFn(Function):
             db = torch.empty(C, dtype=torch.float32, device=x2.device)
             nbytes = lib.fmmt_mlp_ln_bwd_input_workspace(C)
             ws = _ws(nbytes, x2.device)
-            rc = lib.fmmt_mlp_ln_bwd_input(dtype_code(dt) | (SAVE_DG if ctx.dg else 0), M, C, _p(dy2), _p(h_pre), _p(_lp(w2, dt, transpose=True)), _p(_lp(w1, dt, transpose=True)),
+            w2t, w1t = _lp(w2, dt, transpose=True), _lp(w1, dt, transpose=True)
+            rc = lib.fmmt_mlp_ln_bwd_input(dtype_code(dt) | (SAVE_DG if ctx.dg else 0), M, C, _p(dy2), _p(h_pre), _p(w2t), _p(w1t),
                                            _p(rowscale), ctx.rps, _p(x2), _p(mean), _p(rstd), _p(g), _p(dh), _p(dx), _p(dg), _p(db), _p(ws), nbytes, _st())
             check(rc, f"fmmt_mlp_ln_bwd_input(M={M},C={C})")
             dw2, db2 = wgrad_raw(dy2, h, True, rowscale, ctx.rps)
@@ -1106,8 +1114,9 @@ def window_block_backward(dy, x2, xn, o, mean, rstd, lse, g, wqkv, bqkv, wproj, 
     if _WBLOCK_BWD and (dt == torch.bfloat16 or (_WBLOCK_F32 and dt == torch.float32 and C == 96)) and (m is None or shift > 0):
         # (fp32: the same entry point runs the generic restatement of the recompute kernel, csrc/wattn_bwd_ref.hip)
         # attention core backward with q, k, v and d(attention output) re-formed inside the kernel (no qkv / d(out) tensors)
-        rc = lib.fmmt_window_block_attn_bwd(dtype_code(dt), n_img, H, W, C, num_heads, shift, _p(xn), _p(dy2), _p(o), _p(lse), _p(_lp(wqkv, dt)),
-                                            _p(bqkv.detach().float().contiguous() if bqkv is not None else None), _p(_lp(wproj, dt)), _p(tab), _p(index_i32),
+        wql, wpl, bqf = _lp(wqkv, dt), _lp(wproj, dt), (bqkv.detach().float().contiguous() if bqkv is not None else None)
+        rc = lib.fmmt_window_block_attn_bwd(dtype_code(dt), n_img, H, W, C, num_heads, shift, _p(xn), _p(dy2), _p(o), _p(lse), _p(wql),
+                                            _p(bqf), _p(wpl), _p(tab), _p(index_i32),
                                             scale, _p(rowscale), _p(dqkv), _p(dtable), _p(ws), nbytes, _st())
         check(rc, "fmmt_window_block_attn_bwd")
     else:

@@ -2,7 +2,8 @@
 as two HIP graphs and the text branch on a second HIP stream, (c) the same plus parallel.GradientAverager (persistent
 bucketed gradients, world size 1) must walk the same trajectory -- same losses, same updated parameters -- over six
 optimisation steps (a ROCm 7.0 HIP-graph defect that corrupts replayed gradients from the third replay on is what this test
-first caught; facialmmt_amd/__init__.py carries the workaround).  Dropout inside the multimodal model is off; Swin's DropPath / Gumbel noise replay from the seed."""
+first caught; facialmmt_amd/__init__.py carries the workaround).  Dropout inside the multimodal model is off; Swin's DropPath / Gumbel noise replay from the seed.
+These are comparisons of this project's steps with each other; tests/test_gpu_step_oracle.py is where the steps meet an independent fp64 reference."""
 import os
 import types
 
