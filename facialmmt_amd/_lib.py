@@ -84,6 +84,16 @@ SIGNATURES = {
     "fmmt_eval_accumulate": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, C.c_int64, C.c_int64, _p]),
 }
 
+# include/fmmt_pool_head.h, one to one.  Why a second table and a second header (which fmmt.h includes) instead of three more rows above:
+# tests/test_eval_cpu.py pins len(SIGNATURES) == 59 and tests/test_host_cpu.py holds fmmt.h's own prototypes equal to SIGNATURES; both files stay as
+# they are, so the pooling head's entry points are declared beside them.  tests/test_unimodal_oracle_cpu.py::test_pool_head_header_signatures_and_library_agree
+# holds this table, that header (names and the type of every argument) and the built library together.
+POOL_HEAD_SIGNATURES = {
+    "fmmt_pool_head_bwd_workspace": (_sz, [_i, _i, _i]),
+    "fmmt_pool_head_fwd": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _u64, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "fmmt_pool_head_bwd": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+}
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -104,7 +114,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1786,3 +1786,94 @@ def eval_accumulate(logits, labels, acc, logits_out=None, out_offset=0, pred=Tru
     check(_lib.load().fmmt_eval_accumulate(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), a, a + 8, a + 16, _p(out), _p(logits_out), int(out_offset),
                                            int(cap), _st()), f"fmmt_eval_accumulate(B={B},NL={NL})")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# additive-attention pooling -> dropout -> classifier -> cross-entropy (csrc/pool_head.hip)
+# ------------------------------------------------------------------------------------------------
+def _pool_head_args(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels):
+    _need_cuda(h, "pool_head_loss")
+    if h.dim() != 3 or ph.shape != h.shape or ph.dtype != h.dtype:
+        raise _lib.FmmtError(f"pool_head_loss: h and ph must be (B, L, H) tensors of one dtype, got {tuple(h.shape)} {h.dtype} / {tuple(ph.shape)} {ph.dtype}")
+    B, L, H = h.shape
+    if cls_w.dim() != 2 or cls_w.shape[1] != H:
+        raise _lib.FmmtError(f"pool_head_loss: the classifier weight must be (NL, {H}), got {tuple(cls_w.shape)}")
+    NL = cls_w.shape[0]
+    if qq.numel() != H or value_w.numel() != H or value_b.numel() != 1 or tuple(mask.shape) != (B, L) or cls_b.shape != (NL,) or tuple(labels.shape) != (B,):
+        raise _lib.FmmtError(f"pool_head_loss: qq / value_w ({H},), value_b (1,), mask ({B}, {L}), cls_b ({NL},), labels ({B},) expected")
+    # contiguous fp32 tensors (the modules' parameters, the mask, a qq already cast by the caller) pass through as views: no launch
+    f32 = [_c16(t.detach().reshape(-1).float()) for t in (qq, value_w, value_b, mask, cls_w, cls_b)]
+    lab = labels.detach().to(device=h.device, dtype=torch.int64).contiguous()
+    return (B, L, H, NL), _c16(h.detach()), _c16(ph.detach()), f32, lab
+
+
+def pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0):
+    """fmmt_pool_head_fwd on tensors (no autograd).  h, ph (B, L, H) bf16 / fp32; the rest as the modules hold them (any shape with the right element
+    count, read as fp32); seed: python int or a 1-element int64 CUDA tensor.  Returns (loss (), logits (B, NL), alpha (B, L), pooled (B, H), keep (B, H)),
+    all fp32."""
+    (B, L, H, NL), h2, ph2, (q, vw, vb, mk, cw, cb), lab = _pool_head_args(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels)
+    dev = h2.device
+    lib = _lib.load()
+    logits = torch.empty((B, NL), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    alpha = torch.empty((B, L), dtype=torch.float32, device=dev)
+    pooled, keep = torch.empty((B, H), dtype=torch.float32, device=dev), torch.empty((B, H), dtype=torch.float32, device=dev)
+    nbytes = lib.fmmt_pool_head_bwd_workspace(B, L, H)
+    ws = _ws(nbytes, dev)
+    seed_t = seed if isinstance(seed, torch.Tensor) else None
+    seed_i = 0 if seed_t is not None else int(seed)
+    check(lib.fmmt_pool_head_fwd(dtype_code(h2.dtype), B, L, H, NL, _p(h2), _p(ph2), _p(q), _p(vw), _p(vb), _p(mk), _p(cw), _p(cb), _p(lab), float(p), seed_i,
+                                 _p(seed_t), _p(logits), _p(loss), _p(alpha), _p(pooled), _p(keep), _p(ws), nbytes, _st()),
+          f"fmmt_pool_head_fwd(B={B},L={L},H={H},NL={NL})")
+    return loss, logits, alpha, pooled, keep
+
+
+def pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep):
+    """fmmt_pool_head_bwd on tensors: (dh_pool, dph) in h's dtype, (dqq (H,), dv (H,), dvb (1,), dW (NL, H), db (NL,)) fp32"""
+    B, L, H = h.shape
+    NL = cls_w.shape[0]
+    dev = h.device
+    lib = _lib.load()
+    h2, ph2 = _c16(h.detach()), _c16(ph.detach())
+    q, vw, cw = (_c16(t.detach().reshape(-1).float()) for t in (qq, value_w, cls_w))
+    dl = dloss.detach().reshape(-1).float().contiguous()
+    dh, dph = torch.empty_like(h2), torch.empty_like(h2)
+    dqq, dv = torch.empty((H,), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.float32, device=dev)
+    dvb = torch.empty((1,), dtype=torch.float32, device=dev)
+    dW, db = torch.empty((NL, H), dtype=torch.float32, device=dev), torch.empty((NL,), dtype=torch.float32, device=dev)
+    nbytes = lib.fmmt_pool_head_bwd_workspace(B, L, H)
+    ws = _ws(nbytes, dev)
+    check(lib.fmmt_pool_head_bwd(dtype_code(h2.dtype), B, L, H, NL, _p(dl), _p(h2), _p(ph2), _p(q), _p(vw), _p(cw), _p(labels), _p(logits), _p(alpha), _p(pooled),
+                                 _p(keep), _p(dh), _p(dph), _p(dqq), _p(dv), _p(dvb), _p(dW), _p(db), _p(ws), nbytes, _st()),
+          f"fmmt_pool_head_bwd(B={B},L={L},H={H},NL={NL})")
+    return dh, dph, dqq, dv, dvb, dW, db
+
+
+class PoolHeadLossFn(Function):
+    """(loss, logits) of the V-only classifier's tail behind ph = P h + b_P and qq = Q query_vector + b_Q (modules/Transformer.py:24-45, src/models.py:219-221,
+    train.py:258): two launches forward, two backward (csrc/pool_head.hip).  The gradient flows from the loss; the logits are returned for the caller's
+    bookkeeping and are not differentiable.  Saved: alpha, the pooled vector, the keep mask (the dropout is not replayed: B x H values)."""
+
+    @staticmethod
+    def forward(ctx, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed):
+        _need_cuda(h, "pool_head_loss")
+        lab = labels.detach().to(device=h.device, dtype=torch.int64).contiguous()      # once: the raw call below finds it as it needs it
+        loss, logits, alpha, pooled, keep = pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed)
+        ctx.save_for_backward(h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep)
+        ctx.shapes = (qq.shape, value_w.shape, value_b.shape, cls_w.shape, cls_b.shape)
+        ctx.dtypes = (qq.dtype, value_w.dtype, value_b.dtype, cls_w.dtype, cls_b.dtype)
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep = ctx.saved_tensors
+        dh, dph, dqq, dv, dvb, dW, db = pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep)
+        sh, dt = ctx.shapes, ctx.dtypes
+        outs = [g.reshape(s).to(d) for g, s, d in zip((dqq, dv, dvb, dW, db), sh, dt)]
+        return dh.reshape(h.shape), dph.reshape(h.shape), outs[0], outs[1], outs[2], None, outs[3], outs[4], None, None, None
+
+
+def pool_head_loss(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0):
+    """-> (loss, logits): mean cross-entropy of classifier(dropout(additive-attention pooling of h)) and the logits (see PoolHeadLossFn)"""
+    return PoolHeadLossFn.apply(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed)

@@ -1787,3 +1787,139 @@ class AuxStep:
                 self.sched.step()
             self.opt.zero_grad(set_to_none=True)
         return loss.detach()
+
+
+class UnimodalStep:
+    """One V-only training step, train.py:245-273 (choice_modality 'V'): meld_utt_transformer on pre-extracted face features -> cross-entropy /
+    trg_accumulation_steps -> backward; every trg_accumulation_steps micro-steps clip over the model's parameters (args.clip), optimizer step,
+    scheduler step, gradients cleared.  batch = (modality_feature, utterance_mask, labels); returns the detached micro-loss.  The tail behind the
+    encoder -- pooling, dropout, classifier, loss -- is models.meld_utt_transformer.forward_loss (ops.pool_head_loss)."""
+
+    def __init__(self, model, optimizer, scheduler, args):
+        self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
+        self.i_batch = 0
+
+    def __call__(self, batch):
+        feature, mask, labels = batch
+        loss, _ = self.model.forward_loss(feature, mask, labels)
+        loss = loss / self.args.trg_accumulation_steps
+        loss.backward()
+        self.i_batch += 1
+        if self.i_batch % self.args.trg_accumulation_steps == 0:
+            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.args.clip)
+            self.opt.step()
+            if self.sched is not None:
+                self.sched.step()
+            self.opt.zero_grad(set_to_none=True)
+        return loss.detach()
+
+    def start_epoch(self):
+        """a partial accumulation window does not carry into the next epoch (train.py:250-251 restart per epoch)"""
+        self.i_batch = 0
+        self.opt.zero_grad(set_to_none=True)
+
+
+class GraphedUnimodalStep:
+    """UnimodalStep as two HIP graphs, the construction of GraphedAuxStep: graph A = bf16 shadow refresh, forward_loss, backward, gradient hand-over into
+    flat fp32 buffers (+ the clip norm); graph B = clip + optimizer step (one fused launch for AdamW / HFAdamW with a device learning rate).  The warm-up
+    passes run on a side stream and are undone (parameter snapshot, optimizer state zeroed); the dropout seeds are drawn on the device inside graph A,
+    so every replay draws fresh masks.  The batch shape is the captured one: another shape raises ValueError -- a short last batch of an epoch goes
+    through UnimodalStep on the same model and optimizer."""
+
+    def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2):
+        from .parallel import GradientAverager
+        self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
+        self.autocast_dtype = autocast_dtype
+        feature, mask, labels = batch
+        self.feature, self.mask, self.labels = feature.clone(), mask.clone(), torch.as_tensor(labels, device=feature.device).clone()
+        self.shadows = None
+        self.i_batch = 0
+        dev = feature.device
+        self.flat = GradientAverager(self.model.parameters(), hooks=False)
+        self.flat_view_of = {p: p.grad for p in self.flat.params}
+        self.pairs = [(p, p) for p in self.flat.params]
+        self.fused = FusedClipAdamW(optimizer, self.flat.params, self.flat_view_of, {}, args.clip) if FusedClipAdamW.eligible(optimizer, self.flat.params) else None
+        self.handover = FusedHandOver(len(self.flat.params)) if (self.fused is not None and FUSED_HANDOVER) else None
+        for p in self.flat.params:
+            p.grad = None
+        self.accumulate = args.trg_accumulation_steps > 1
+        snap = [(t, t.detach().clone()) for t in list(self.model.parameters()) + list(self.model.buffers())]
+        rng = torch.cuda.get_rng_state(dev)
+        cap = distinct_stream(dev)
+        cap.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(cap):
+            for _ in range(warmup_iters):
+                self._fwd_bwd()
+                self._update()
+        torch.cuda.current_stream().wait_stream(cap)
+        torch.cuda.synchronize(dev)
+        _restore(snap)
+        del snap
+        _reset_optimizer_state(self.opt)
+        if self.fused is not None:
+            self.fused.reset()
+        self.flat.zero_grad()
+        torch.cuda.set_rng_state(rng, dev)
+        self.shadows = _pin_shadows([self.model])
+        self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with capture_window(), _ops_pinned_scope(self.shadows):
+            with torch.cuda.graph(self.graph_a, stream=cap):
+                self.loss = self._fwd_bwd()
+            with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
+                self._update()
+        _KEEP_GRAPHS.append((self.graph_a, self.graph_b))
+        self.flat.zero_grad()
+
+    def _fwd_bwd(self):
+        if self.shadows is not None:
+            self.shadows.refresh()
+        if self.autocast_dtype is not None:
+            with torch.autocast("cuda", dtype=self.autocast_dtype, cache_enabled=False):
+                loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels)
+        else:
+            loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels)
+        self.logits = logits.detach()
+        loss = loss / self.args.trg_accumulation_steps
+        loss.backward()
+        if self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm):
+            self.fused.norm_ready = True
+        else:
+            _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
+        return loss.detach()
+
+    def _update(self):
+        if self.fused is not None:
+            self.fused.update()
+        else:
+            for p in self.flat.params:
+                p.grad = self.flat_view_of[p]
+            torch.nn.utils.clip_grad_norm_(self.flat.params, self.args.clip)
+            self.opt.step()
+        if self.accumulate:
+            self.flat.zero_grad()
+        for p in self.flat.params:                           # the next backward must produce fresh gradient tensors
+            p.grad = None
+
+    def __call__(self, batch):
+        feature, mask, labels = batch
+        if tuple(feature.shape) != tuple(self.feature.shape) or tuple(mask.shape) != tuple(self.mask.shape) or tuple(labels.shape) != tuple(self.labels.shape):
+            raise ValueError(f"GraphedUnimodalStep: batch of shape {tuple(feature.shape)} / {tuple(mask.shape)} / {tuple(labels.shape)}, captured for "
+                             f"{tuple(self.feature.shape)} / {tuple(self.mask.shape)} / {tuple(self.labels.shape)}")
+        with torch.no_grad():
+            if feature is not self.feature:
+                self.feature.copy_(feature, non_blocking=True)
+                self.mask.copy_(mask, non_blocking=True)
+                self.labels.copy_(labels, non_blocking=True)
+        self.graph_a.replay()
+        self.i_batch += 1
+        if self.i_batch % self.args.trg_accumulation_steps == 0:
+            self.graph_b.replay()
+            _bump_versions(self.flat.params)
+            if self.sched is not None:
+                self.sched.step()
+        return self.loss
+
+    def start_epoch(self):
+        """a partial accumulation window does not carry into the next epoch (train.py:250-251 restart per epoch)"""
+        self.i_batch = 0
+        self.flat.zero_grad()

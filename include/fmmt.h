@@ -510,6 +510,11 @@ int fmmt_emotion_head_fwd(int dtype, int N, int K, int H, int NL, const void* fe
 int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, const int64_t* labels, double* loss_sum, int64_t* count,
                          int64_t* confusion, int32_t* pred, float* logits_out, int64_t out_offset, int64_t out_capacity, void* stream);
 
+/* The V-only classifier's tail -- additive-attention pooling -> dropout -> classifier -> cross-entropy (fmmt_pool_head_fwd / _bwd / _bwd_workspace:
+ * modules/Transformer.py:24-45, src/models.py:219-221, train.py:258) -- is declared in a header of its own, included here, so that the prototypes
+ * of THIS file stay the set the existing ABI tests pin (59 names, equal to _lib.SIGNATURES); its own test holds it to _lib.POOL_HEAD_SIGNATURES. */
+#include "fmmt_pool_head.h"
+
 #ifdef __cplusplus
 }
 #endif
