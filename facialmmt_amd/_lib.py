@@ -94,6 +94,15 @@ POOL_HEAD_SIGNATURES = {
     "fmmt_pool_head_bwd": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
+# include/fmmt_ragged.h, one to one: a third table and header for the reason written above POOL_HEAD_SIGNATURES
+# (tests/test_ragged_cpu.py::test_ragged_header_signatures_and_library_agree holds table, header and library together)
+RAGGED_SIGNATURES = {
+    "fmmt_pack_frames": (_i, [_i, _i, _i, _sz, _p, _p, _p, _p, _p]),
+    "fmmt_batchnorm1d_fwd_n": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _f, _i, _p, _p, _p, _p]),
+    "fmmt_batchnorm1d_bwd_n": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "fmmt_select_frames_fwd_n": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p]),
+}
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -114,7 +123,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

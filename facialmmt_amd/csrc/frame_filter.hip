@@ -22,7 +22,8 @@ template <typename T>
 __global__ __launch_bounds__(FF_THREADS) void select_frames_fwd_kernel(int nF, int NL, int B, int Lv, int D, const float* __restrict__ preds,
                                                                        const T* __restrict__ vin, const float* __restrict__ vmask,
                                                                        const long long* __restrict__ num_imgs, float threshold, T* __restrict__ out,
-                                                                       float* __restrict__ new_mask, int* __restrict__ src_face) {
+                                                                       float* __restrict__ new_mask, int* __restrict__ src_face,
+                                                                       const int* __restrict__ n_valid) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* cum = reinterpret_cast<int*>(smem);                  // [nF]   inclusive prefix sum of `owned`
     int* slot = cum + nF;                                     // [B*Lv] face feeding the slot (selection branch), -1 = empty
@@ -32,10 +33,11 @@ __global__ __launch_bounds__(FF_THREADS) void select_frames_fwd_kernel(int nF, i
     int* run = before + B;                                    // [B]    leading run of ones of vision_mask[u] (fallback branch)
     int* offs = run + B;                                      // [B]    faces in front of utterance u in the fallback enumeration
     int* part = offs + B;                                     // [FF_THREADS] scan partials
-    __shared__ int n_sel;
+    __shared__ int n_sel, n_real;                             // n_real: the faces the "did any face pass" decision looks at (fmmt_select_frames_fwd_n)
     const int tid = threadIdx.x;
     if (tid == 0) {
         n_sel = 0;
+        n_real = n_valid ? min(*n_valid, nF) : nF;              // rows behind it are padding of a fixed-capacity batch (ragged.hip): read once per workgroup
         long long c = 0;
         for (int u = 0; u < B; ++u) {
             const long long n = num_imgs[u];
@@ -50,12 +52,12 @@ __global__ __launch_bounds__(FF_THREADS) void select_frames_fwd_kernel(int nF, i
     const int CH = (nF + FF_THREADS - 1) / FF_THREADS;
     const int g0 = tid * CH, g1 = min(g0 + CH, nF);
     int local = 0, sel_local = 0;
-    const int last_upper = upper[B - 1];
+    const int last_upper = upper[B - 1], real_end = n_real;
     for (int g = g0; g < g1; ++g) {
         float imp = 0.f;
         for (int j = 0; j < NL; ++j) { const float p = preds[(size_t)g * NL + j]; imp += p * p; }
         const bool sel = imp > threshold;
-        sel_local += sel ? 1 : 0;
+        sel_local += (sel && g < real_end) ? 1 : 0;
         local += (sel && g < last_upper) ? 1 : 0;
         cum[g] = (sel && g < last_upper) ? 1 : 0;
     }
@@ -147,9 +149,10 @@ size_t ff_lds(int nF, int B, int Lv) { return ((size_t)nF + (size_t)B * Lv + 5 *
 
 }  // namespace
 
-extern "C" int fmmt_select_frames_fwd(int dtype, int nF, int NL, int B, int Lv, int D, const float* preds, const void* vision_inputs,
-                                      const float* vision_mask, const int64_t* num_imgs, float threshold, void* out, float* new_mask,
-                                      int32_t* src_face, void* stream) {
+// fmmt_select_frames_fwd (n_valid == NULL: every row of preds is a face) and fmmt_select_frames_fwd_n (include/fmmt_ragged.h)
+static int select_frames_fwd_launch(int dtype, int nF, int NL, int B, int Lv, int D, const float* preds, const void* vision_inputs,
+                                    const float* vision_mask, const int64_t* num_imgs, float threshold, void* out, float* new_mask,
+                                    int32_t* src_face, const int32_t* n_valid, void* stream) {
     if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
     if (nF <= 0 || nF > 8192 || NL <= 0 || NL > FF_THREADS || B <= 0 || B > 256 || Lv <= 0 || B * Lv > 8192 || D <= 0) return FMMT_EINVAL;
     if (!preds || !vision_inputs || !vision_mask || !num_imgs || !out || !new_mask || !src_face) return FMMT_EINVAL;
@@ -161,15 +164,27 @@ extern "C" int fmmt_select_frames_fwd(int dtype, int nF, int NL, int B, int Lv, 
         static FmmtLdsOnce once;
         if (int rc = once.set(reinterpret_cast<const void*>(&select_frames_fwd_kernel<bf16>), 96 * 1024)) return rc;
         hipLaunchKernelGGL(select_frames_fwd_kernel<bf16>, dim3(grid), dim3(FF_THREADS), lds, st, nF, NL, B, Lv, D, preds, (const bf16*)vision_inputs, vision_mask,
-                           (const long long*)num_imgs, threshold, (bf16*)out, new_mask, src_face);
+                           (const long long*)num_imgs, threshold, (bf16*)out, new_mask, src_face, n_valid);
     } else {
         static FmmtLdsOnce once;
         if (int rc = once.set(reinterpret_cast<const void*>(&select_frames_fwd_kernel<float>), 96 * 1024)) return rc;
         hipLaunchKernelGGL(select_frames_fwd_kernel<float>, dim3(grid), dim3(FF_THREADS), lds, st, nF, NL, B, Lv, D, preds, (const float*)vision_inputs, vision_mask,
-                           (const long long*)num_imgs, threshold, (float*)out, new_mask, src_face);
+                           (const long long*)num_imgs, threshold, (float*)out, new_mask, src_face, n_valid);
     }
     FMMT_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int fmmt_select_frames_fwd(int dtype, int nF, int NL, int B, int Lv, int D, const float* preds, const void* vision_inputs,
+                                      const float* vision_mask, const int64_t* num_imgs, float threshold, void* out, float* new_mask,
+                                      int32_t* src_face, void* stream) {
+    return select_frames_fwd_launch(dtype, nF, NL, B, Lv, D, preds, vision_inputs, vision_mask, num_imgs, threshold, out, new_mask, src_face, nullptr, stream);
+}
+
+extern "C" int fmmt_select_frames_fwd_n(int dtype, int nF, int NL, int B, int Lv, int D, const float* preds, const void* vision_inputs,
+                                        const float* vision_mask, const int64_t* num_imgs, float threshold, void* out, float* new_mask,
+                                        int32_t* src_face, const int32_t* n_valid, void* stream) {
+    return select_frames_fwd_launch(dtype, nF, NL, B, Lv, D, preds, vision_inputs, vision_mask, num_imgs, threshold, out, new_mask, src_face, n_valid, stream);
 }
 
 extern "C" int fmmt_select_frames_bwd(int dtype, int nF, int NL, int B, int Lv, int D, const void* dout, const int32_t* src_face, float* dpreds,

@@ -2,6 +2,7 @@
 // run as a GEMM on the gathered patches), BatchNorm1d of the embedding head, the cross-modal input
 // embedding (scale + sinusoidal position with the zero-is-padding rule) and an elementwise scale.
 #include "fmmt_common.h"
+#include "bn1d_core.h"
 #include "../../include/fmmt.h"
 
 namespace {
@@ -28,61 +29,13 @@ __global__ void patch_cols_kernel(const T* __restrict__ src, T* __restrict__ dst
     else *reinterpret_cast<uint4*>(d) = *reinterpret_cast<const uint4*>(s);
 }
 
-// BatchNorm1d over (n, C) rows: a workgroup of 1024 threads = 64 columns x 16 row groups; every column sum is sixteen per-group partial
-// sums (rows g, g + 16, ...) added in group order through LDS -- fixed order, two passes (mean, then centred squares) as before.
-// (One thread per column walking all n rows serially, the round-1 form, took 295 us forward and 250 us backward for the 640 x 512 head
-//  of the bench step: three dependent passes of 640 loads.)
-constexpr int BN_COLS = 64, BN_GROUPS = 16;
-
-__device__ __forceinline__ float bn_colsum(float v, float (*red)[BN_COLS], int tc, int tg) {
-    __syncthreads();                                        // the previous use of `red` is over
-    red[tg][tc] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int g = 0; g < BN_GROUPS; ++g) s += red[g][tc];
-    return s;
-}
-
+// BatchNorm1d of the embedding head: the kernel bodies live in bn1d_core.h (shared with the row-masked entry points of ragged.hip)
 template <typename T>
 __global__ __launch_bounds__(BN_COLS * BN_GROUPS) void bn1d_fwd_kernel(int n, int C, const T* __restrict__ x, const float* __restrict__ gamma,
                                 const float* __restrict__ beta, float* running_mean, float* running_var,
                                 float momentum, float eps, int training, T* __restrict__ y,
                                 float* save_mean, float* save_invstd) {
-    __shared__ float red[BN_GROUPS][BN_COLS];
-    const int tc = threadIdx.x % BN_COLS, tg = threadIdx.x / BN_COLS;
-    const int c = blockIdx.x * BN_COLS + tc;
-    const bool ok = c < C;
-    float mean, invstd;
-    if (training) {
-        float s = 0.f;
-        if (ok)
-            for (int r = tg; r < n; r += BN_GROUPS) s += to_f32(x[(size_t)r * C + c]);
-        mean = bn_colsum(s, red, tc, tg) / n;
-        float q = 0.f;
-        if (ok)
-            for (int r = tg; r < n; r += BN_GROUPS) {
-                const float d = to_f32(x[(size_t)r * C + c]) - mean;
-                q += d * d;
-            }
-        q = bn_colsum(q, red, tc, tg);
-        const float var = q / n;
-        invstd = rsqrtf(var + eps);
-        if (ok && tg == 0) {
-            running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
-            running_var[c] = (1.f - momentum) * running_var[c] + momentum * (n > 1 ? q / (n - 1) : var);
-        }
-    } else {
-        mean = ok ? running_mean[c] : 0.f;
-        invstd = ok ? rsqrtf(running_var[c] + eps) : 0.f;
-    }
-    if (!ok) return;
-    if (tg == 0) {
-        if (save_mean) save_mean[c] = mean;
-        if (save_invstd) save_invstd[c] = invstd;
-    }
-    const float g = gamma[c] * invstd, b = beta[c] - mean * g;
-    for (int r = tg; r < n; r += BN_GROUPS) y[(size_t)r * C + c] = from_f32<T>(to_f32(x[(size_t)r * C + c]) * g + b);
+    bn1d_fwd_body<T, false>(n, n, C, x, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd);
 }
 
 template <typename T>
@@ -90,35 +43,7 @@ __global__ __launch_bounds__(BN_COLS * BN_GROUPS) void bn1d_bwd_kernel(int n, in
                                 const float* __restrict__ gamma, const float* __restrict__ save_mean,
                                 const float* __restrict__ save_invstd, int training, T* __restrict__ dx,
                                 float* dgamma, float* dbeta) {
-    __shared__ float red[BN_GROUPS][BN_COLS];
-    const int tc = threadIdx.x % BN_COLS, tg = threadIdx.x / BN_COLS;
-    const int c = blockIdx.x * BN_COLS + tc;
-    const bool ok = c < C;
-    const float mean = ok ? save_mean[c] : 0.f, invstd = ok ? save_invstd[c] : 0.f;
-    float sb = 0.f, sg = 0.f;
-    if (ok)
-        for (int r = tg; r < n; r += BN_GROUPS) {
-            const float g = to_f32(dy[(size_t)r * C + c]);
-            sb += g;
-            sg += g * (to_f32(x[(size_t)r * C + c]) - mean) * invstd;
-        }
-    sb = bn_colsum(sb, red, tc, tg);
-    sg = bn_colsum(sg, red, tc, tg);
-    if (!ok) return;
-    if (tg == 0) {
-        if (dgamma) dgamma[c] = sg;
-        if (dbeta) dbeta[c] = sb;
-    }
-    const float k = gamma[c] * invstd;
-    if (training) {
-        const float inv_n = 1.f / n;
-        for (int r = tg; r < n; r += BN_GROUPS) {
-            const float xh = (to_f32(x[(size_t)r * C + c]) - mean) * invstd;
-            dx[(size_t)r * C + c] = from_f32<T>(k * (to_f32(dy[(size_t)r * C + c]) - sb * inv_n - xh * sg * inv_n));
-        }
-    } else {
-        for (int r = tg; r < n; r += BN_GROUPS) dx[(size_t)r * C + c] = from_f32<T>(k * to_f32(dy[(size_t)r * C + c]));
-    }
+    bn1d_bwd_body<T, false>(n, n, C, dy, x, gamma, save_mean, save_invstd, training, dx, dgamma, dbeta);
 }
 
 template <typename T>

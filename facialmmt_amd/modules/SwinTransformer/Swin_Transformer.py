@@ -425,21 +425,22 @@ class SwinTransformer(nn.Module):
     def no_weight_decay_keywords(self):
         return {'relative_position_bias_table'}
 
-    def _head(self, x):
+    def _head(self, x, n_valid=None):
         ln, _, fc, bn = self.output_layer
         x = ops.layer_norm(x, ln.weight, ln.bias, ln.eps)
         x = ops.linear(x.reshape(x.shape[0], -1), fc.weight, fc.bias)
         use_batch = self.training or not bn.track_running_stats
         if self.training and bn.track_running_stats:
             bn.num_batches_tracked += 1
-        return ops.batch_norm_1d(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, use_batch)
+        # n_valid: the rows behind it are padding of a fixed-capacity batch (ops.pack_frames) -- this BatchNorm is the one op of the model that mixes rows
+        return ops.batch_norm_1d(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, use_batch, n_valid=n_valid)
 
     # uint8 input (B, S, S, 3): which library's bicubic the fused pre-step reproduces ('pil': Aff-Wild2 path, pinned
     # bit-exactly; 'cv2': MELD path, unpinned) and the activation dtype it produces (None: the parameters' dtype)
     input_resize = "pil"
     input_dtype = None
 
-    def forward_features(self, x):
+    def forward_features(self, x, n_valid=None):
         _require(self.pos_drop.p == 0.0 or not self.training, "pos_drop p > 0 in training")
         if x.dtype == torch.uint8:
             x = self.patch_embed.forward_u8(x, self.input_resize, self.input_dtype)
@@ -448,9 +449,13 @@ class SwinTransformer(nn.Module):
         self._draw_drop_paths(x.shape[0], x.device)
         for layer in self.layers:
             x = layer(x)
-        return self._head(x)
+        return self._head(x, n_valid)
 
-    def forward(self, x):
+    def forward(self, x, n_valid=None):
+        """n_valid (1-element int32 device tensor; None: the reference's forward): x holds a fixed capacity of frames, the first n_valid real --
+        the head's BatchNorm then runs over those rows (one real frame: what the duplication below computes, by its arithmetic)"""
+        if n_valid is not None:
+            return self.forward_features(x, n_valid)
         if len(x) == 1:                              # BatchNorm needs two samples (ref :535-538)
             return self.forward_features(torch.cat((x, x), dim=0))[:1]
         return self.forward_features(x)

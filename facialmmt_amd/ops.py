@@ -1394,7 +1394,7 @@ class SelectFramesFn(Function):
     """train_step.select_frames as one launch per direction (fmmt_select_frames_fwd / _bwd; train.py:75-114)."""
 
     @staticmethod
-    def forward(ctx, preds, vision_inputs, vision_mask, num_imgs, threshold):
+    def forward(ctx, preds, vision_inputs, vision_mask, num_imgs, threshold, n_valid=None):
         _need_cuda(preds, "select_frames")
         nF, NL = preds.shape
         B, Lv, D = vision_inputs.shape
@@ -1405,8 +1405,13 @@ class SelectFramesFn(Function):
         out = torch.empty((B, Lv, D + NL), dtype=vin.dtype, device=vin.device)
         new_mask = torch.empty((B, Lv), dtype=torch.float32, device=vin.device)
         src = torch.empty((B, Lv), dtype=torch.int32, device=vin.device)
-        check(_lib.load().fmmt_select_frames_fwd(dtype_code(vin.dtype), nF, NL, B, Lv, D, _p(p32), _p(vin), _p(vm), _p(n), float(threshold), _p(out),
-                                                 _p(new_mask), _p(src), _st()), f"fmmt_select_frames_fwd(nF={nF},B={B},Lv={Lv},D={D})")
+        if n_valid is None:
+            check(_lib.load().fmmt_select_frames_fwd(dtype_code(vin.dtype), nF, NL, B, Lv, D, _p(p32), _p(vin), _p(vm), _p(n), float(threshold), _p(out),
+                                                     _p(new_mask), _p(src), _st()), f"fmmt_select_frames_fwd(nF={nF},B={B},Lv={Lv},D={D})")
+        else:                                                # preds rows >= n_valid are padding of a fixed-capacity batch (pack_frames)
+            check(_lib.load().fmmt_select_frames_fwd_n(dtype_code(vin.dtype), nF, NL, B, Lv, D, _p(p32), _p(vin), _p(vm), _p(n), float(threshold), _p(out),
+                                                       _p(new_mask), _p(src), _p(_n_valid_word(n_valid, preds.device, "select_frames")), _st()),
+                  f"fmmt_select_frames_fwd_n(nF={nF},B={B},Lv={Lv},D={D})")
         ctx.save_for_backward(src)
         ctx.cfg = (nF, NL, B, Lv, D, preds.dtype)
         new_mask = new_mask.to(vision_mask.dtype)
@@ -1420,7 +1425,7 @@ class SelectFramesFn(Function):
         dout = dout.contiguous()
         dp = torch.empty((nF, NL), dtype=torch.float32, device=dout.device)
         check(_lib.load().fmmt_select_frames_bwd(dtype_code(dout.dtype), nF, NL, B, Lv, D, _p(dout), _p(src), _p(dp), _st()), "fmmt_select_frames_bwd")
-        return dp.to(pdt), None, None, None, None
+        return dp.to(pdt), None, None, None, None, None
 
 
 def select_frames_fusable(preds, vision_inputs, vision_mask):
@@ -1429,8 +1434,10 @@ def select_frames_fusable(preds, vision_inputs, vision_mask):
             and preds.shape[0] <= 8192 and B <= 256 and B * Lv <= 8192 and preds.shape[1] <= 256)
 
 
-def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold):
-    return SelectFramesFn.apply(preds, vision_inputs, vision_mask, num_imgs, float(threshold))
+def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold, n_valid=None):
+    """n_valid (1-element int32 CUDA tensor, pack_frames' counts): rows of preds at or behind it are padding and take no part in the
+    "did any face pass" decision; None: every row is a face"""
+    return SelectFramesFn.apply(preds, vision_inputs, vision_mask, num_imgs, float(threshold), n_valid)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1678,8 +1685,76 @@ class BatchNorm1dFn(Function):
         return dx, dg, db, None, None, None, None, None
 
 
-def batch_norm_1d(x, gamma, beta, running_mean, running_var, momentum, eps, training):
+def batch_norm_1d(x, gamma, beta, running_mean, running_var, momentum, eps, training, n_valid=None):
+    """n_valid (1-element int32 CUDA tensor): only the first n_valid rows of x are real -- BatchNorm1dNFn; None: every row"""
+    if n_valid is not None:
+        return BatchNorm1dNFn.apply(x, gamma, beta, running_mean, running_var, momentum, eps, training, n_valid)
     return BatchNorm1dFn.apply(x, gamma, beta, running_mean, running_var, momentum, eps, training)
+
+
+# ------------------------------------------------------------------------------------------------
+# ragged frame counts behind one fixed shape (csrc/ragged.hip, include/fmmt_ragged.h)
+# ------------------------------------------------------------------------------------------------
+def _n_valid_word(n_valid, device, what):
+    """the device word the *_n entry points read: an int32 CUDA tensor (its first element counts: pack_frames' `counts` passes as it is)"""
+    if not torch.is_tensor(n_valid) or n_valid.dtype != torch.int32 or not n_valid.is_cuda or n_valid.device != device or n_valid.numel() < 1:
+        raise _lib.FmmtError(f"{what}: n_valid must be an int32 tensor on {device} (the row count is read on the device: no host synchronisation)")
+    return n_valid
+
+
+def pack_frames(frames, num_imgs, capacity):
+    """(B, Lv, ...) frames as the loader pads them + num_imgs (B,) -> (packed (capacity, ...), counts): the real frames in the reference's
+    concatenation order (train.py:60-71: torch.cat([frames[u, :n_u] for u])) at the front, zeros behind, in ONE launch without a host
+    synchronisation (fmmt_pack_frames).  counts: int32 (2,) on the device, [min(total, capacity), total]; counts is what the n_valid arguments of
+    batch_norm_1d / select_frames take.  Frames behind `capacity` are dropped (counts[1] > capacity).  Any dtype whose row is a multiple of 16 bytes."""
+    _need_cuda(frames, "pack_frames")
+    if frames.dim() < 3:
+        raise ValueError(f"pack_frames expects (B, Lv, ...) frames, got {tuple(frames.shape)}")
+    f = frames.detach().contiguous()
+    B, Lv = f.shape[0], f.shape[1]
+    row_bytes = f[0, 0].numel() * f.element_size()
+    n = torch.as_tensor(num_imgs).to(device=f.device, dtype=torch.int64).contiguous()
+    if tuple(n.shape) != (B,):
+        raise ValueError(f"pack_frames: num_imgs must hold one count per utterance ({B}), got {tuple(n.shape)}")
+    capacity = int(capacity)
+    packed = torch.empty((max(capacity, 0),) + tuple(f.shape[2:]), dtype=f.dtype, device=f.device)
+    counts = torch.empty(2, dtype=torch.int32, device=f.device)
+    check(_lib.load().fmmt_pack_frames(B, Lv, capacity, row_bytes, _p(f), _p(n), _p(packed), _p(counts), _st()),
+          f"fmmt_pack_frames(B={B},Lv={Lv},capacity={capacity},row_bytes={row_bytes})")
+    return packed, counts
+
+
+class BatchNorm1dNFn(Function):
+    """BatchNorm1d over the first n_valid rows of x (fmmt_batchnorm1d_fwd_n / _bwd_n): statistics and column sums over those rows, zeros in
+    y / dx behind them.  One launch per direction, as BatchNorm1dFn; n_valid == x.shape[0] gives its bits."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, training, n_valid):
+        _need_cuda(x, "batch_norm")
+        x = x.contiguous()
+        nv = _n_valid_word(n_valid, x.device, "batch_norm_1d")
+        g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        n, C = x.shape
+        y = torch.empty_like(x)
+        sm = torch.empty(C, dtype=torch.float32, device=x.device)
+        si = torch.empty(C, dtype=torch.float32, device=x.device)
+        check(_lib.load().fmmt_batchnorm1d_fwd_n(dtype_code(x.dtype), n, C, _p(nv), _p(x), _p(g), _p(b), _p(running_mean), _p(running_var),
+                                                 momentum, eps, int(training), _p(y), _p(sm), _p(si), _st()), "fmmt_batchnorm1d_fwd_n")
+        ctx.save_for_backward(x, g, sm, si, nv)
+        ctx.training = bool(training)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, g, sm, si, nv = ctx.saved_tensors
+        n, C = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        dg = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+        check(_lib.load().fmmt_batchnorm1d_bwd_n(dtype_code(x.dtype), n, C, _p(nv), _p(dy), _p(x), _p(g), _p(sm), _p(si), int(ctx.training),
+                                                 _p(dx), _p(dg), _p(db), _st()), "fmmt_batchnorm1d_bwd_n")
+        return dx, dg, db, None, None, None, None, None, None
 
 
 class PosEmbScaleFn(Function):

@@ -15,21 +15,25 @@ import torch.nn.functional as F
 SELECT_FRAMES_KERNEL = True      # module constant (tests patch it): False = the torch restatement below (~55 launches)
 
 
-def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold):
+def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold, n_valid=None):
     """Device-side, sync-free version of train.py:75-114.
 
     preds (sumF, 7): per-face emotion distribution (Gumbel-softmax of the Swin logits), differentiable;
     vision_inputs (B, Lv, D); vision_mask (B, Lv); num_imgs (B,) int tensor of real frames per utterance.
     Faces with sum(p^2) > threshold are kept; each utterance packs its kept faces to the front
     (new mask = count of kept faces) together with the matching rows of vision_inputs; if no face at all
-    passes, every real frame is kept.  Returns (vision_inputs_concat (B,Lv,D+7), new_vision_mask (B,Lv))."""
+    passes, every real frame is kept.  Returns (vision_inputs_concat (B,Lv,D+7), new_vision_mask (B,Lv)).
+
+    n_valid (a 1-element integer tensor on preds' device, ops.pack_frames' counts; None: every row is a face): preds holds a fixed
+    capacity of rows of which the first n_valid are faces.  "No face at all passes" (train.py:80,84) is then decided over those rows
+    only; ownership needs nothing (an owned face lies below sum(num_imgs) - (B - 1) <= n_valid)."""
     B, Lv, D = vision_inputs.shape
     dev = preds.device
     nF = preds.shape[0]
     if SELECT_FRAMES_KERNEL and torch.is_tensor(num_imgs):
         from . import ops
         if ops.select_frames_fusable(preds, vision_inputs, vision_mask):
-            return ops.select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold)      # one launch (csrc/frame_filter.hip): same index arithmetic
+            return ops.select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold, n_valid)      # one launch (csrc/frame_filter.hip): same index arithmetic
     n = torch.as_tensor(num_imgs).to(dev).long()
     importance = (preds * preds).sum(dim=1)                       # == diag(P P^T)
     sel = importance > threshold                                   # (nF,)
@@ -58,11 +62,24 @@ def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold):
     offs = torch.cumsum(real_cnt, 0) - real_cnt
     idx_all = (offs.view(B, 1) + torch.arange(Lv, device=dev).view(1, Lv)).clamp(max=nF - 1)
     emo_all = preds[idx_all] * real.unsqueeze(-1).to(preds.dtype)
-    any_sel = sel.any()
+    any_sel = sel.any() if n_valid is None else (sel & (g < n_valid.reshape(-1)[0])).any()
     emo = torch.where(any_sel, emo_sel, emo_all)
     inputs = torch.where(any_sel, inp_sel, vision_inputs)
     mask = torch.where(any_sel, mask_sel, vision_mask)
     return torch.cat((inputs, emo.to(inputs.dtype)), dim=-1), mask
+
+
+def check_frame_total(num_imgs, Lv, capacity):
+    """Host-side guard of a packed step (frame_capacity): with num_imgs as the reference's collate yields it -- a list or a CPU tensor -- the
+    number of real frames, sum(clamp(n, 0, Lv)), must fit the capacity the step was built for; ValueError otherwise, before anything is launched.
+    A device tensor is not read here (that would be a host synchronisation): the step's `frame_counts` then tells (counts[1] > capacity)."""
+    if torch.is_tensor(num_imgs):
+        if num_imgs.is_cuda:
+            return
+        num_imgs = num_imgs.tolist()
+    total = sum(min(max(int(n), 0), int(Lv)) for n in num_imgs)
+    if total > capacity:
+        raise ValueError(f"the batch holds {total} face frames, the step was built for frame_capacity={capacity}")
 
 
 def pick_concurrent_stream(device, candidates: int = 8, cycles: int = 4_000_000):
@@ -235,10 +252,15 @@ class TargetStep:
     auxiliary task's optimizer (train.py:31), so its gradients are dropped after each step."""
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, autocast_dtype=None, ddp_model=None, averager=None,
-                 discarded_swin_gradients="compute"):
+                 discarded_swin_gradients="compute", frame_capacity=None):
         """Data parallel: pass `averager` (parallel.GradientAverager over the multimodal parameters) or, alternatively,
         `ddp_model` (the module wrapped by torch's DistributedDataParallel).
-        `discarded_swin_gradients`: "compute" (default, what the reference executes) or "skip" -- see SKIP_NOTE."""
+        `discarded_swin_gradients`: "compute" (default, what the reference executes) or "skip" -- see SKIP_NOTE.
+        `frame_capacity` (None: `frames` is the compact (sum num_imgs, ...) tensor): the batch carries `frames` as the loader pads them,
+        (B, Lv, ...), and the step packs them on the device into `frame_capacity` rows (ops.pack_frames), runs Swin on all of them with the
+        head's BatchNorm over the real ones and filters with the same row count -- GraphedTargetStep(frame_capacity=...) launch by launch."""
+        self.frame_capacity = None if frame_capacity is None else int(frame_capacity)
+        self.frame_counts = None                             # packed path: ops.pack_frames' counts of the last step (device, int32 [n_valid, total])
         if discarded_swin_gradients not in ("compute", "skip"):
             raise ValueError("discarded_swin_gradients: 'compute' or 'skip'")
         self.skip_swin_bwd = discarded_swin_gradients == "skip"
@@ -283,6 +305,13 @@ class TargetStep:
         if evs is not None:
             mark("start")
         from .parallel import GradientAverager, accumulate
+        n_valid, swin_kw = None, {}
+        if self.frame_capacity is not None:
+            check_frame_total(num_imgs, frames.shape[1], self.frame_capacity)
+            from . import ops
+            num_imgs = torch.as_tensor(num_imgs).to(frames.device)
+            frames, n_valid = ops.pack_frames(frames, num_imgs, self.frame_capacity)
+            self.frame_counts, swin_kw = n_valid, {"n_valid": n_valid}
         self.i_batch += 1
         last = self.i_batch % args.trg_accumulation_steps == 0
         if getattr(self.mm, "text_stream", None) is not None:
@@ -294,11 +323,11 @@ class TargetStep:
                 self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
         if self.skip_swin_bwd:
             with torch.no_grad():
-                preds = self.swin(frames, is_trg_task=True)
+                preds = self.swin(frames, is_trg_task=True, **swin_kw)
         else:
-            preds = self.swin(frames, is_trg_task=True)                              # (sumF, 7), Gumbel-softmax
+            preds = self.swin(frames, is_trg_task=True, **swin_kw)                   # (sumF, 7), Gumbel-softmax
         mark("swin_fwd")
-        vis_concat, new_mask = select_frames(preds.float(), vision_inputs, vision_mask, num_imgs, args.FacialEmoImpor_threshold)
+        vis_concat, new_mask = select_frames(preds.float(), vision_inputs, vision_mask, num_imgs, args.FacialEmoImpor_threshold, n_valid)
         mark("frame_filter")
         # gradient exchange only on the last micro-step of the window; torch's DDP decides in its FORWARD whether the
         # coming backward synchronises, so the no_sync context has to cover the forward as well
@@ -1063,7 +1092,7 @@ class GraphedTargetStep:
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
-                 swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False):
+                 swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None):
         """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
@@ -1075,7 +1104,14 @@ class GraphedTargetStep:
         discarded) -- the prefetched forward sees the weights the in-order forward would; a Swin parameter whose version moved since the prefetch
         (an auxiliary step ran in between) makes the step redo the forward in order.  Why: per step ~22 ms of the GPU's time are streams of small
         launches at low occupancy (text encoder forward and the tail of its backward, the fusion stack, the update) that a 14 ms block of
-        chip-filling Swin kernels can run beside; every step still executes exactly one Swin forward."""
+        chip-filling Swin kernels can run beside; every step still executes exactly one Swin forward.
+        `frame_capacity` (None: `frames` is the compact (sum num_imgs, ...) tensor and every batch must have the captured number of frames): an
+        integer F_cap makes the step train on RAGGED batches with one capture.  The sample `batch` and every later one carry `frames` as the
+        loader pads them, (B, Lv, ...), with num_imgs the real counts; the capture holds ops.pack_frames (real frames to the front of F_cap rows,
+        the count in a device word) -> Swin on all F_cap rows with the head's BatchNorm over the real ones -> the frame filter with the same count.
+        num_imgs as a list or CPU tensor (the reference's collate) is checked against F_cap on the host (ValueError); a device tensor is the
+        caller's contract and `frame_counts` (int32 [n_valid, total], device) is there for a check at the end of an epoch.  Default single-graph
+        mode only: NotImplementedError together with pipeline_swin / branch_graphs / fork_streams / an active averager."""
         import os
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
@@ -1084,6 +1120,15 @@ class GraphedTargetStep:
         self.pipeline = bool(pipeline_swin)
         self.branches = bool(branch_graphs)                 # BRANCH_NOTE below
         self.forked = bool(fork_streams)                    # FORK_NOTE at _fwd_bwd_forked
+        self.frame_capacity = None if frame_capacity is None else int(frame_capacity)
+        self.frame_counts = None
+        if self.frame_capacity is not None:
+            if self.pipeline or self.branches or self.forked or bool(getattr(averager, "active", False)):
+                raise NotImplementedError("frame_capacity: the default single-graph mode on one rank (not with pipeline_swin / branch_graphs / "
+                                          "fork_streams / an active gradient exchange)")
+            if self.frame_capacity < 1 or batch[8].dim() < 3:
+                raise ValueError("frame_capacity: a positive number of frames, and `frames` as the loader pads them, (B, Lv, ...)")
+            check_frame_total(batch[9], batch[8].shape[1], self.frame_capacity)
         if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0":
             raise RuntimeError("GraphedTargetStep: DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in the environment before the HIP "
                                "runtime initialises (see facialmmt_amd/__init__.py)")
@@ -1367,6 +1412,14 @@ class GraphedTargetStep:
                 self.sched.step()
         return self.loss, self.new_mask
 
+    def _swin_preds(self, frames, num_imgs):
+        """Swin's target-task forward on the step's frames; with a frame capacity: packed on the device first (-> self.frame_counts)"""
+        if self.frame_capacity is None:
+            return self.swin(frames, is_trg_task=True)
+        from . import ops
+        packed, self.frame_counts = ops.pack_frames(frames, num_imgs, self.frame_capacity)
+        return self.swin(packed, is_trg_task=True, n_valid=self.frame_counts)
+
     def _swin_forward(self, frames):
         """pipeline_swin, graph S: Swin's forward alone (its bf16 shadows refreshed at the head: an auxiliary step may have moved the weights)"""
         if self.swin_shadows is not None:
@@ -1419,7 +1472,7 @@ class GraphedTargetStep:
             pass
         elif self.skip_swin_bwd:
             with torch.no_grad():
-                preds = self.swin(frames, is_trg_task=True)
+                preds = self._swin_preds(frames, num_imgs)
         else:
             if not whole:
                 # two-piece backward: the cut goes INSIDE Swin, behind stage SWIN_CUT (below): the first piece then holds the text
@@ -1429,7 +1482,7 @@ class GraphedTargetStep:
                 layers = getattr(getattr(self.swin, "swin", None), "layers", None)
                 if layers is not None and len(layers) > self.SWIN_CUT + 1:
                     hook = layers[self.SWIN_CUT].register_forward_hook(lambda m, i, o: cut.__setitem__("x", o))
-            preds = self.swin(frames, is_trg_task=True)
+            preds = self._swin_preds(frames, num_imgs)
             if hook is not None:
                 hook.remove()
             if fork_hook is not None:
@@ -1437,7 +1490,8 @@ class GraphedTargetStep:
                 if "out" not in box:                        # the hooked module was not called through __call__ on this path
                     launch_text()
                 pending = box["out"]
-        vis_concat, new_mask = select_frames(preds.float(), vision_inputs, vision_mask, num_imgs, args.FacialEmoImpor_threshold)
+        vis_concat, new_mask = select_frames(preds.float(), vision_inputs, vision_mask, num_imgs, args.FacialEmoImpor_threshold,
+                                             self.frame_counts if self.frame_capacity is not None else None)
         with ac():
             if pending is None:
                 pending = mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
@@ -1574,6 +1628,8 @@ class GraphedTargetStep:
             return self._call_pipelined(batch, next_batch)
         if self.branches:
             return self._call_branches(batch)
+        if self.frame_capacity is not None:
+            check_frame_total(batch[9], self.static[8].shape[1], self.frame_capacity)
         with torch.no_grad():
             for i, (dst, src) in enumerate(zip(self.static, batch)):
                 if dst is src:

@@ -514,6 +514,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
  * modules/Transformer.py:24-45, src/models.py:219-221, train.py:258) -- is declared in a header of its own, included here, so that the prototypes
  * of THIS file stay the set the existing ABI tests pin (59 names, equal to _lib.SIGNATURES); its own test holds it to _lib.POOL_HEAD_SIGNATURES. */
 #include "fmmt_pool_head.h"
+/* Ragged frame counts behind one captured shape (device-side packing, the row-masked BatchNorm1d, the frame filter's n_valid): likewise, held to _lib.RAGGED_SIGNATURES. */
+#include "fmmt_ragged.h"
 
 #ifdef __cplusplus
 }
