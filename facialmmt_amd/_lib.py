@@ -103,6 +103,12 @@ RAGGED_SIGNATURES = {
     "fmmt_select_frames_fwd_n": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p]),
 }
 
+# include/fmmt_eval_collect.h, one to one: a fourth table and header for the same reason
+# (tests/test_eval_collect_cpu.py::test_eval_collect_header_signatures_and_library_agree holds table, header and library together)
+EVAL_COLLECT_SIGNATURES = {
+    "fmmt_eval_accumulate_at": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int64, _p]),
+}
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -123,7 +129,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

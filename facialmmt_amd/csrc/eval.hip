@@ -13,6 +13,8 @@
 // fmmt_eval_accumulate: per-row fp32 log-sum-exp cross entropy and argmax, added into accumulators that stay on the device for the whole split
 //   (loss sum as a double, row count and the NL x NL confusion matrix as int64).  ONE workgroup; the row losses are summed by a fixed 1024-leaf tree
 //   in LDS, whatever B is, so the sum is deterministic; the counts go through integer LDS atomics (order-free) and leave with ordinary stores.
+// fmmt_eval_accumulate_at (include/fmmt_eval_collect.h): the same update, the rows of the batch also kept -- logits, label, argmax -- at a row index
+//   read from a device word that the kernel then advances, so that a captured graph collects a whole split; same body, same accumulator bits.
 #include "fmmt_common.h"
 #include "../../include/fmmt.h"
 
@@ -90,11 +92,15 @@ __global__ __launch_bounds__(EH_THREADS) void emotion_head_kernel(int N, int K, 
     }
 }
 
+// The body both metric-update kernels share -- ONE statement of the row loss, the argmax, the 1024-leaf loss tree and the LDS confusion counts, so
+// the two entry points leave the same bits in the accumulators.  Row `tid` of the batch is kept at row `base + tid` of logits_out / labels_out /
+// pred_out when that row exists (0 <= base + tid < cap; each pointer may be NULL); `pred` is indexed by the batch row.  Every thread of the
+// workgroup passes the barriers below, whatever B is.
 template <typename T>
-__global__ __launch_bounds__(EA_THREADS) void eval_accumulate_kernel(int B, int NL, const T* __restrict__ logits, int ld, const long long* __restrict__ labels,
-                                                                     double* __restrict__ loss_sum, long long* __restrict__ count,
-                                                                     long long* __restrict__ confusion, int* __restrict__ pred,
-                                                                     float* __restrict__ logits_out, long long out_offset) {
+__device__ __forceinline__ void eval_accumulate_body(int B, int NL, const T* __restrict__ logits, int ld, const long long* __restrict__ labels,
+                                                     double* __restrict__ loss_sum, long long* __restrict__ count, long long* __restrict__ confusion,
+                                                     int* __restrict__ pred, float* __restrict__ logits_out, long long* __restrict__ labels_out,
+                                                     int* __restrict__ pred_out, long long base, long long cap) {
     __shared__ double red[EA_THREADS];
     __shared__ int conf[EH_MAXNL * EH_MAXNL];
     __shared__ int cnt;
@@ -118,11 +124,16 @@ __global__ __launch_bounds__(EA_THREADS) void eval_accumulate_kernel(int B, int 
         const float lse = m + logf(z);
         const long long label = labels[tid];
         if (pred != nullptr) pred[tid] = arg;
-        if (logits_out != nullptr) {
-            float* o = logits_out + (size_t)(out_offset + tid) * NL;
+        const long long dst = base + tid;
+        if (dst >= 0 && dst < cap) {                         // a row behind the capacity is counted below and kept nowhere
+            if (logits_out != nullptr) {
+                float* o = logits_out + (size_t)dst * NL;
 #pragma unroll
-            for (int c = 0; c < EH_MAXNL; ++c)
-                if (c < NL) o[c] = v[c];
+                for (int c = 0; c < EH_MAXNL; ++c)
+                    if (c < NL) o[c] = v[c];
+            }
+            if (labels_out != nullptr) labels_out[dst] = label;
+            if (pred_out != nullptr) pred_out[dst] = arg;
         }
         if (label >= 0 && label < NL) {                      // negative: ignored (torch's ignore_index, padded rows); >= NL can address nothing here
             float vl = 0.f;
@@ -144,6 +155,30 @@ __global__ __launch_bounds__(EA_THREADS) void eval_accumulate_kernel(int B, int 
         *loss_sum += red[0];
         *count += cnt;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(EA_THREADS) void eval_accumulate_kernel(int B, int NL, const T* __restrict__ logits, int ld, const long long* __restrict__ labels,
+                                                                     double* __restrict__ loss_sum, long long* __restrict__ count,
+                                                                     long long* __restrict__ confusion, int* __restrict__ pred,
+                                                                     float* __restrict__ logits_out, long long out_offset) {
+    // the host has checked out_offset + B <= capacity: every row has a place
+    eval_accumulate_body<T>(B, NL, logits, ld, labels, loss_sum, count, confusion, pred, logits_out, nullptr, nullptr, out_offset, out_offset + B);
+}
+
+// The same update with the destination row held in a DEVICE word: a captured graph freezes its launch arguments, a word in memory it re-reads on
+// every replay.  All 1024 threads read *cursor, then a barrier, and only behind the whole body thread 0 advances it: without the barrier a late
+// wave of a B = 1024 batch could read the advanced value and keep its rows B too far.
+template <typename T>
+__global__ __launch_bounds__(EA_THREADS) void eval_accumulate_at_kernel(int B, int NL, const T* __restrict__ logits, int ld, const long long* __restrict__ labels,
+                                                                        double* __restrict__ loss_sum, long long* __restrict__ count,
+                                                                        long long* __restrict__ confusion, long long* cursor,
+                                                                        float* __restrict__ logits_out, long long* __restrict__ labels_out,
+                                                                        int* __restrict__ pred_out, long long out_capacity) {
+    const long long base = *cursor;
+    __syncthreads();                                         // every thread holds the old cursor before anything below may write the new one
+    eval_accumulate_body<T>(B, NL, logits, ld, labels, loss_sum, count, confusion, nullptr, logits_out, labels_out, pred_out, base, out_capacity);
+    if (threadIdx.x == 0) *cursor = base + B;                // also when rows were dropped: cursor > out_capacity reports the overflow
 }
 
 }  // namespace
@@ -178,6 +213,24 @@ extern "C" int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits
     else
         hipLaunchKernelGGL(eval_accumulate_kernel<float>, dim3(1), dim3(EA_THREADS), 0, st, B, NL, (const float*)logits, ld, (const long long*)labels, loss_sum,
                            (long long*)count, (long long*)confusion, pred, logits_out, (long long)out_offset);
+    FMMT_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fmmt_eval_accumulate_at(int dtype, int B, int NL, const void* logits, int ld, const int64_t* labels, double* loss_sum, int64_t* count,
+                                       int64_t* confusion, int64_t* cursor, float* logits_out, int64_t* labels_out, int32_t* pred_out,
+                                       int64_t out_capacity, void* stream) {
+    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
+    if (B <= 0 || B > EA_THREADS || NL <= 0 || NL > EH_MAXNL || ld < NL || out_capacity < 0) return FMMT_EINVAL;
+    if (!logits || !labels || !loss_sum || !count || !confusion || !cursor || !logits_out || !labels_out) return FMMT_EINVAL;
+    if (((uintptr_t)loss_sum | (uintptr_t)count | (uintptr_t)confusion | (uintptr_t)labels | (uintptr_t)cursor | (uintptr_t)labels_out) & 7) return FMMT_EALIGN;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == FMMT_BF16)
+        hipLaunchKernelGGL(eval_accumulate_at_kernel<bf16>, dim3(1), dim3(EA_THREADS), 0, st, B, NL, (const bf16*)logits, ld, (const long long*)labels, loss_sum,
+                           (long long*)count, (long long*)confusion, (long long*)cursor, logits_out, (long long*)labels_out, pred_out, (long long)out_capacity);
+    else
+        hipLaunchKernelGGL(eval_accumulate_at_kernel<float>, dim3(1), dim3(EA_THREADS), 0, st, B, NL, (const float*)logits, ld, (const long long*)labels, loss_sum,
+                           (long long*)count, (long long*)confusion, (long long*)cursor, logits_out, (long long*)labels_out, pred_out, (long long)out_capacity);
     FMMT_CHECK_LAUNCH();
     return 0;
 }

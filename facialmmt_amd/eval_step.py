@@ -6,13 +6,22 @@ launch, train_step.select_frames) -> multimodal forward -> loss / argmax / confu
 ops.eval_accumulate).  `EvalStep` issues that launch by launch; `GraphedEvalStep` captures it once as a single HIP graph (text encoder as the one
 fork branch) and replays it per batch.  `MeldMetrics` owns the accumulators; the only device-to-host copy of a split is `MeldMetrics.result()`.
 
+Real MELD batches are ragged: the loader pads the frames to (B, Lv, ...) and says how many are real (utils/dataset.py:275-292), and the compact
+tensor the reference concatenates (train.py:167-178) has another first dimension in almost every batch.  `frame_capacity` on either step takes the
+padded batch instead: ops.pack_frames moves the real frames to the front of a fixed number of rows on the device, Swin and the head run on all of
+them, and the frame filter is told how many are real.  `GraphedEvalStep` captures one graph per capacity ("bucket") and replays the smallest that
+holds the batch; `MeldMetrics(collect_rows=...)` keeps the split's logits and labels at a device-held row index (ops.eval_accumulate_at), so
+`evaluate` clones nothing per batch.
+
 Departures from the reference, on purpose:
   * the loss is `sum of row losses / rows`, exact for any batch sizes; the reference multiplies each batch MEAN by args.trg_batch_size and divides
     by the split size, which is the same number when every batch is full and over-weights a short last batch otherwise;
   * `f1_per_class` always has num_labels entries (0 for a class that occurs neither as label nor as prediction); scikit-learn's
     `f1_score(average=None)` without `labels=`, as the reference calls it, returns fewer values when a class is absent from both vectors;
   * `gumbel="off"` (not the default) evaluates without the Gumbel noise: the reference keeps F.gumbel_softmax in evaluation too, so its score is a
-    random variable of the generator state; "off" is the deterministic variant."""
+    random variable of the generator state; "off" is the deterministic variant.  With `frame_capacity` the noise is drawn for every row of the
+    capacity, so under "sample" the numbers a given seed hands to a given frame -- and with them the score -- also depend on the capacity, i.e.
+    on which bucket a batch was replayed in: one more way in which that score is a draw, not a constant.  "off" does not depend on the bucket."""
 from __future__ import annotations
 
 import contextlib
@@ -22,7 +31,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .train_step import _KEEP_GRAPHS, _ops_pinned_scope, _pin_shadows, capture_window, distinct_stream, fused_inference, select_frames
+from .train_step import (_KEEP_GRAPHS, _ops_pinned_scope, _pin_shadows, capture_window, check_frame_total, distinct_stream, fused_inference,
+                         select_frames)
 
 EMOTIONS = ("Neutral", "Surprise", "Fear", "Sadness", "Joy", "Disgust", "Anger")      # class order of eval_meld (utils/eval_metrics.py:27)
 
@@ -64,20 +74,39 @@ def eval_meld(results, truths, test=False):
 
 class MeldMetrics:
     """Loss sum, row count and confusion matrix of a split, accumulated on the device: `update` is one launch and no synchronisation,
-    `result()` one device-to-host copy of 2 + num_labels^2 numbers (51 for MELD's 7 classes)."""
+    `result()` one device-to-host copy of 2 + num_labels^2 numbers (51 for MELD's 7 classes).
 
-    def __init__(self, num_labels: int = 7, device="cuda"):
+    `collect_rows` (None: nothing below exists): the metrics also COLLECT the split -- `results` (collect_rows, num_labels) fp32, `truths`
+    (collect_rows,) int64 and `cursor`, one int64 device word -- through ops.eval_accumulate_at: every update stores its rows at the cursor and
+    advances it on the device, so the update inside a captured graph fills the buffers front to back.  Rows behind collect_rows are counted and
+    not kept; `collected()` then raises.  The cursor lives behind the accumulators in one allocation: one copy brings both to the host."""
+
+    def __init__(self, num_labels: int = 7, device="cuda", collect_rows=None):
         if not 1 <= num_labels <= 8:
             raise ValueError("MeldMetrics: 1..8 classes (fmmt_eval_accumulate)")
         self.num_labels = num_labels
-        self.acc = torch.zeros(2 + num_labels * num_labels, dtype=torch.int64, device=device)
+        self.collect_rows = None if collect_rows is None else int(collect_rows)
+        n = 2 + num_labels * num_labels
+        if self.collect_rows is None:
+            self.acc = torch.zeros(n, dtype=torch.int64, device=device)
+            return
+        if self.collect_rows < 0:
+            raise ValueError("MeldMetrics: collect_rows is a number of rows")
+        self.words = torch.zeros(n + 1, dtype=torch.int64, device=device)          # accumulators | cursor
+        self.acc, self.cursor = self.words[:n], self.words[n:]
+        self.results = torch.zeros(self.collect_rows, num_labels, dtype=torch.float32, device=device)
+        self.truths = torch.zeros(self.collect_rows, dtype=torch.int64, device=device)
 
     def reset(self):
-        self.acc.zero_()                                      # in place: a captured graph keeps writing to this tensor
+        (self.acc if self.collect_rows is None else self.words).zero_()          # in place: a captured graph keeps writing to this tensor
 
     def update(self, logits, labels, logits_out=None, out_offset=0, pred=False):
         """logits (B, num_labels), labels (B,) with negative = ignored (rows a caller padded); B <= 1024"""
-        return ops.eval_accumulate(logits, labels, self.acc, logits_out, out_offset, pred=pred)
+        if self.collect_rows is None:
+            return ops.eval_accumulate(logits, labels, self.acc, logits_out, out_offset, pred=pred)
+        if logits_out is not None or pred:
+            raise ValueError("MeldMetrics(collect_rows=...): the rows go to `results` / `truths` at the cursor; logits_out / pred are the other mode")
+        return ops.eval_accumulate_at(logits, labels, self.acc, self.cursor, self.results, self.truths)
 
     @staticmethod
     def summarise(host: np.ndarray, num_labels: int):
@@ -90,9 +119,30 @@ class MeldMetrics:
         return types.SimpleNamespace(avg_loss=loss_sum / count if count else float("nan"), weighted_f1=weighted, f1_per_class=f1, confusion=conf,
                                      count=count, loss_sum=loss_sum)
 
+    @staticmethod
+    def collected_count(host: np.ndarray, collect_rows: int) -> int:
+        """the host half of collected(): `host` = the 2 + NL^2 + 1 int64 words as copied from the device, the cursor last.  The rows kept, or
+        ValueError when more rows went through update() than the buffers hold"""
+        cursor = int(np.asarray(host).ravel()[-1])
+        if cursor > collect_rows:
+            raise ValueError(f"MeldMetrics: {cursor} rows went through update(), the buffers were built for collect_rows={collect_rows}: "
+                             f"the rows behind it were counted and not kept")
+        return max(cursor, 0)
+
+    def _host(self):
+        return (self.acc if self.collect_rows is None else self.words).cpu().numpy()
+
     def result(self):
         """avg_loss (= loss sum / rows), weighted_f1, f1_per_class (always num_labels values, order EMOTIONS), confusion [label][prediction], count"""
-        return self.summarise(self.acc.cpu().numpy(), self.num_labels)
+        return self.summarise(self._host()[:2 + self.num_labels ** 2], self.num_labels)
+
+    def collected(self, host=None):
+        """(results[:n], truths[:n]), n = the rows updated since reset(): views of the buffers, valid until the next reset() / update().  `host`:
+        the words a caller already copied (evaluate() reads cursor and accumulators in one copy)"""
+        if self.collect_rows is None:
+            raise ValueError("MeldMetrics was built without collect_rows: nothing is collected")
+        n = self.collected_count(self._host() if host is None else host, self.collect_rows)
+        return self.results[:n], self.truths[:n]
 
 
 # ------------------------------------------------------------------------------------------------ one batch
@@ -118,10 +168,22 @@ def _autocast(dtype):
     return torch.autocast("cuda", dtype=dtype) if dtype is not None else contextlib.nullcontext()
 
 
-def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_stream=None, shadows=None):
-    """the launches of one evaluation batch on the current stream (text encoder on `text_stream`, forked and joined, when given)"""
+def _check_padded_frames(frames, vision_inputs):
+    if frames.dim() < 3 or tuple(frames.shape[:2]) != tuple(vision_inputs.shape[:2]):
+        raise ValueError(f"frame_capacity: `frames` as the loader pads them, (B, Lv, ...) = {tuple(vision_inputs.shape[:2])} + the frame's shape, "
+                         f"got {tuple(frames.shape)} (the compact (sum num_imgs, ...) tensor belongs to a step without frame_capacity)")
+
+
+def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_stream=None, shadows=None, frame_capacity=None):
+    """the launches of one evaluation batch on the current stream (text encoder on `text_stream`, forked and joined, when given).  With a
+    `frame_capacity` the batch's frames are the padded (B, Lv, ...) tensor: checked on the host where num_imgs lives there, packed on the device,
+    and everything up to the frame filter runs on `frame_capacity` rows.  Returns (logits, kept-frame mask, importance, frame counts or None)."""
     (ids, attn_mask, sep_mask, audio, audio_mask, vision_inputs, vision_mask, labels, frames, num_imgs, utt_idx) = batch
     dev = frames.device
+    counts = None
+    if frame_capacity is not None:                           # both checks read host values only and come before the first launch
+        _check_padded_frames(frames, vision_inputs)
+        check_frame_total(num_imgs, frames.shape[1], frame_capacity)
     main = torch.cuda.current_stream()
     if shadows is not None:
         shadows.refresh()
@@ -138,10 +200,14 @@ def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_
             text_feat, text_mask = text()
     else:
         text_feat, text_mask = text()
+    n_imgs = torch.as_tensor(num_imgs, device=dev)
+    if frame_capacity is not None:
+        # in eval() the embedding head's BatchNorm normalises with its running statistics, row by row: Swin needs no row count, the filter does
+        frames, counts = ops.pack_frames(frames, n_imgs, frame_capacity)
     feats = swin.swin(frames)
     noise = ops.gumbel_noise(feats.shape[0], swin.num_labels, dev) if sample else None
     preds, importance = ops.emotion_head(feats, swin.linear, swin.classifier, swin.tau, noise)
-    vis_concat, new_mask = select_frames(preds, vision_inputs, vision_mask, torch.as_tensor(num_imgs, device=dev), args.FacialEmoImpor_threshold)
+    vis_concat, new_mask = select_frames(preds, vision_inputs, vision_mask, n_imgs, args.FacialEmoImpor_threshold, n_valid=counts)
     if text_stream is not None:
         main.wait_stream(text_stream)
         text_feat.record_stream(main)
@@ -149,7 +215,7 @@ def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_
     with _autocast(autocast_dtype):
         logits = mm.fusion_branch(text_feat, text_mask, audio, audio_mask, vis_concat, new_mask)
     metrics.update(logits, torch.as_tensor(labels, device=dev))
-    return logits, new_mask, importance
+    return logits, new_mask, importance, counts
 
 
 def _check_gumbel(gumbel):
@@ -162,18 +228,55 @@ class EvalStep:
     """One batch of multimodal_evaluate (train.py:154-243), launch by launch, under no_grad with both models in eval(): Swin features ->
     ops.emotion_head -> select_frames -> multimodal forward -> MeldMetrics.update.  Same batch tuple as train_step.TargetStep.  Returns
     (logits, kept-frame mask); the models are back in their previous train / eval mode afterwards.  Inside the step the fused forwards of
-    train_step.fuse_text_encoder run (train_step.fused_inference)."""
+    train_step.fuse_text_encoder run (train_step.fused_inference).
 
-    def __init__(self, swin_model, multimodal_model, args, autocast_dtype=None, gumbel="sample", metrics=None):
+    `frame_capacity` (None: `frames` is the compact (sum num_imgs, ...) tensor): the meaning it has on train_step.TargetStep.  The batch carries
+    `frames` as the loader pads them, (B, Lv, ...), and num_imgs the real counts; the step packs them into `frame_capacity` rows on the device
+    (ops.pack_frames), runs Swin, the noise and the head on all of them and hands the row count to the frame filter.  num_imgs as a list or CPU
+    tensor is checked on the host (ValueError before anything is launched); with a device tensor `frame_counts` -- the (2,) int32 device tensor
+    [rows packed, frames in the batch] of the last batch -- tells afterwards ([1] > frame_capacity: frames were dropped).  `importance` then has
+    `frame_capacity` rows, of which the first frame_counts[0] mean something: the others are the head's answer to an all-zero frame."""
+
+    def __init__(self, swin_model, multimodal_model, args, autocast_dtype=None, gumbel="sample", metrics=None, frame_capacity=None):
         self.sample = _check_gumbel(gumbel)
+        self.frame_capacity = None if frame_capacity is None else int(frame_capacity)
+        if self.frame_capacity is not None and self.frame_capacity < 1:
+            raise ValueError("frame_capacity: a positive number of frames")
+        self.frame_counts = None
         self.swin, self.mm, self.args, self.autocast_dtype = swin_model, multimodal_model, args, autocast_dtype
         self.metrics = metrics if metrics is not None else MeldMetrics(swin_model.num_labels, next(multimodal_model.parameters()).device)
         self.importance = None
 
     def __call__(self, batch):
         with torch.no_grad(), _eval_mode(self.swin, self.mm), fused_inference():
-            logits, new_mask, self.importance = _forward_batch(self.swin, self.mm, self.args, batch, self.metrics, self.autocast_dtype, self.sample)
+            logits, new_mask, self.importance, self.frame_counts = _forward_batch(self.swin, self.mm, self.args, batch, self.metrics, self.autocast_dtype,
+                                                                                  self.sample, frame_capacity=self.frame_capacity)
         return logits, new_mask
+
+
+def pick_bucket(num_imgs, Lv, buckets):
+    """The capacity a ragged batch is replayed in: the smallest of the ascending `buckets` that holds its sum(clamp(num_imgs, 0, Lv)) real frames
+    when num_imgs is on the host (a list or CPU tensor, as the reference's collate yields it); the LARGEST for a device tensor, which is not
+    read here (that would be a host synchronisation).  A host total above the largest bucket: ValueError, before anything is launched."""
+    if torch.is_tensor(num_imgs):
+        if num_imgs.is_cuda:
+            return buckets[-1]
+        num_imgs = num_imgs.tolist()
+    total = sum(min(max(int(n), 0), int(Lv)) for n in num_imgs)
+    for c in buckets:
+        if total <= c:
+            return c
+    raise ValueError(f"the batch holds {total} face frames, the step was built for frame_capacity={buckets[-1]}")
+
+
+def _clamp_counts(num_imgs, Lv, capacity):
+    """the sample batch's counts cut down, utterance by utterance, until their total fits `capacity`: what a bucket below the sample's total is captured on"""
+    out, room = [], int(capacity)
+    for n in (num_imgs.tolist() if torch.is_tensor(num_imgs) else num_imgs):
+        k = min(max(int(n), 0), int(Lv), room)
+        out.append(k)
+        room -= k
+    return out
 
 
 class GraphedEvalStep:
@@ -182,50 +285,92 @@ class GraphedEvalStep:
     graph.  A batch of other shapes (the short last batch of a split) runs through an EvalStep on the same MeldMetrics; rows a caller padded
     carry a negative label.  The graph has a memory pool of its own and writes nothing the training graphs read except the bf16 weight
     shadows, which it rebuilds from the current parameters at its head exactly as they do.  The returned logits / mask are the graph's static
-    outputs: clone what must survive the next call."""
+    outputs: clone what must survive the next call.
 
-    def __init__(self, swin_model, multimodal_model, args, batch, autocast_dtype=None, gumbel="sample", metrics=None, overlap_text=True, warmup_iters=2):
+    `frame_capacity` (None: the above, and a batch whose compact frame tensor has another number of rows is "another shape"): an int, or an
+    ascending tuple of ints ("buckets"), makes the step evaluate RAGGED batches by replay.  The sample `batch` and every later one carry
+    `frames` as the loader pads them, (B, Lv, ...), with num_imgs the real counts (EvalStep's docstring).  One graph is captured per capacity;
+    they share the static input buffers and the MeldMetrics, and no captured shape depends on the counts (a bucket below the sample batch's
+    total is warmed up and captured with the sample's counts cut down to fit).  Per batch: num_imgs on the host picks the smallest bucket that
+    holds the batch (`pick_bucket`; a total above the largest is a ValueError before anything is copied or launched); a device tensor takes the
+    largest, without a synchronisation.  A batch whose other shapes differ runs through EvalStep(frame_capacity=largest).  `replays` and
+    `fallbacks` count the two paths on the host; `capacity` is the bucket of the last call, `frame_counts` / `importance` its outputs
+    (`importance` has `capacity` rows, the first frame_counts[0] of them real).  Under gumbel="sample" the noise tensor has the bucket's
+    shape: see the module docstring."""
+
+    def __init__(self, swin_model, multimodal_model, args, batch, autocast_dtype=None, gumbel="sample", metrics=None, overlap_text=True, warmup_iters=2,
+                 frame_capacity=None):
         import os
         if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0":
             raise RuntimeError("GraphedEvalStep: DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in the environment before the HIP runtime "
                                "initialises (see facialmmt_amd/__init__.py)")
         self.sample = _check_gumbel(gumbel)
         self.swin, self.mm, self.args, self.autocast_dtype = swin_model, multimodal_model, args, autocast_dtype
+        self.buckets = None
+        if frame_capacity is not None:
+            self.buckets = tuple(int(c) for c in (frame_capacity if isinstance(frame_capacity, (tuple, list)) else (frame_capacity,)))
+            if not self.buckets or self.buckets[0] < 1 or any(a >= b for a, b in zip(self.buckets, self.buckets[1:])):
+                raise ValueError("frame_capacity: a positive number of frames, or an ascending tuple of them")
+            _check_padded_frames(batch[8], batch[5])
+            check_frame_total(batch[9], batch[8].shape[1], self.buckets[-1])
+        self.replays = self.fallbacks = 0
+        self.capacity = self.frame_counts = None
         dev = batch[8].device
         self.metrics = metrics if metrics is not None else MeldMetrics(swin_model.num_labels, dev)
-        self.eager = EvalStep(swin_model, multimodal_model, args, autocast_dtype, gumbel, self.metrics)
+        self.eager = EvalStep(swin_model, multimodal_model, args, autocast_dtype, gumbel, self.metrics, frame_capacity=self.buckets[-1] if self.buckets else None)
         self.static = [t.clone() if torch.is_tensor(t) else torch.as_tensor(t, device=dev) for t in batch]
         cap = distinct_stream(dev)
         self.text_stream = distinct_stream(dev, (cap,)) if overlap_text else None
-        scratch = MeldMetrics(self.metrics.num_labels, dev)                    # the warm-up passes count into this one
+        collect = getattr(self.metrics, "collect_rows", None)                  # the warm-up passes count into this one, through the same kernel
+        scratch = MeldMetrics(self.metrics.num_labels, dev, collect_rows=None if collect is None else len(batch[7]))
         rng = torch.cuda.get_rng_state(dev)
+        self.graphs = {}
         with torch.no_grad(), _eval_mode(self.swin, self.mm), fused_inference():
-            cap.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(cap):
-                for _ in range(max(1, warmup_iters)):                          # lazy initialisations, the shadow cache the pins are made from
-                    _forward_batch(self.swin, self.mm, args, self.static, scratch, autocast_dtype, self.sample)
-            torch.cuda.current_stream().wait_stream(cap)
-            torch.cuda.synchronize(dev)
-            torch.cuda.set_rng_state(rng, dev)
-            self.shadows = _pin_shadows([self.swin, self.mm])
-            self.graph = torch.cuda.CUDAGraph()
-            with capture_window(), _ops_pinned_scope(self.shadows):
-                with torch.cuda.graph(self.graph, stream=cap):
-                    self.logits, self.new_mask, self.importance = _forward_batch(self.swin, self.mm, args, self.static, self.metrics, autocast_dtype,
-                                                                                 self.sample, self.text_stream, self.shadows)
-        _KEEP_GRAPHS.append((self.graph,))
+            for c in self.buckets or (None,):
+                if c is not None:
+                    self.static[9].copy_(torch.as_tensor(_clamp_counts(batch[9], batch[8].shape[1], c)))
+                cap.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(cap):
+                    for _ in range(max(1, warmup_iters)):                      # lazy initialisations, the shadow cache the pins are made from
+                        scratch.reset()
+                        _forward_batch(self.swin, self.mm, args, self.static, scratch, autocast_dtype, self.sample, frame_capacity=c)
+                torch.cuda.current_stream().wait_stream(cap)
+                torch.cuda.synchronize(dev)
+                torch.cuda.set_rng_state(rng, dev)
+                if not self.graphs:
+                    self.shadows = _pin_shadows([self.swin, self.mm])
+                graph = torch.cuda.CUDAGraph()
+                with capture_window(), _ops_pinned_scope(self.shadows):
+                    with torch.cuda.graph(graph, stream=cap):
+                        outs = _forward_batch(self.swin, self.mm, args, self.static, self.metrics, autocast_dtype, self.sample, self.text_stream,
+                                              self.shadows, frame_capacity=c)
+                self.graphs[c] = (graph, outs)
+                _KEEP_GRAPHS.append((graph,))
+            if self.buckets:
+                self.static[9].copy_(torch.as_tensor(batch[9]))
+        self.graph, (self.logits, self.new_mask, self.importance, _) = self.graphs[self.buckets[-1] if self.buckets else None]
 
     def __call__(self, batch):
         if len(batch) != len(self.static):
             raise ValueError(f"GraphedEvalStep: batch of {len(batch)} entries, captured with {len(self.static)}")
         srcs = [s if torch.is_tensor(s) else torch.as_tensor(s) for s in batch]
+        if self.buckets:
+            _check_padded_frames(srcs[8], srcs[5])                             # the compact tensor is an error, not "another shape"
         if any(tuple(s.shape) != tuple(d.shape) for s, d in zip(srcs, self.static)):
-            return self.eager(batch)
+            out = self.eager(batch)
+            self.fallbacks += 1
+            if self.buckets:
+                self.capacity, self.frame_counts, self.importance = self.buckets[-1], self.eager.frame_counts, self.eager.importance
+            return out
+        c = pick_bucket(batch[9], self.static[8].shape[1], self.buckets) if self.buckets else None
         with torch.no_grad():
             for dst, src in zip(self.static, srcs):
                 if dst is not src:
                     dst.copy_(src, non_blocking=True)
+        self.graph, (self.logits, self.new_mask, self.importance, self.frame_counts) = self.graphs[c]
+        self.capacity = c
         self.graph.replay()
+        self.replays += 1
         return self.logits, self.new_mask
 
 
@@ -249,8 +394,18 @@ def evaluate(step, loader):
     """A whole split through `step` (EvalStep / GraphedEvalStep / UnimodalEvalStep): (avg_loss, results, truths) as multimodal_evaluate /
     unimodal_evaluate return them -- results = the concatenated logits, truths = the concatenated labels, both left on the device.  The one
     host synchronisation is the final copy of the accumulators; step.metrics.result() afterwards has the F1 scores of the same split.
-    avg_loss = loss sum / rows (module docstring)."""
+    avg_loss = loss sum / rows (module docstring).
+
+    When step.metrics collects (MeldMetrics(collect_rows=...)), nothing is cloned per batch: the metric update inside the step has stored every
+    row, and results / truths are `collected()` -- views of the metrics' buffers, valid until its next reset() or update(); ValueError when the
+    split had more rows than collect_rows.  Cursor and accumulators come to the host in the same single copy."""
     step.metrics.reset()
+    if getattr(step.metrics, "collect_rows", None) is not None:
+        for batch in loader:
+            step(batch)
+        host = step.metrics._host()
+        nl = step.metrics.num_labels
+        return (step.metrics.summarise(host[:2 + nl * nl], nl).avg_loss,) + step.metrics.collected(host)
     results, truths = [], []
     for batch in loader:
         out = step(batch)

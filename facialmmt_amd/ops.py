@@ -1863,6 +1863,39 @@ def eval_accumulate(logits, labels, acc, logits_out=None, out_offset=0, pred=Tru
     return out
 
 
+def eval_accumulate_at(logits, labels, acc, cursor, logits_out, labels_out, pred_out=None):
+    """fmmt_eval_accumulate_at: eval_accumulate with the destination row in a DEVICE word, so that a captured graph collects a split.  cursor: int64
+    CUDA tensor of one word; row i of the batch goes to logits_out[cursor + i] ((capacity, NL) fp32), labels_out[cursor + i] ((capacity,) int64)
+    and pred_out[cursor + i] ((capacity,) int32, optional); rows at or behind the capacity are counted and stored nowhere; cursor += B on the
+    device (cursor > capacity afterwards: the split overflowed).  The accumulators get the bits eval_accumulate gives them.  Returns None."""
+    _need_cuda(logits, "eval_accumulate_at")
+    _no_grad_only("eval_accumulate_at", logits)
+    if logits.dim() != 2 or labels.shape != (logits.shape[0],):
+        raise _lib.FmmtError("eval_accumulate_at: logits (B, NL), labels (B,)")
+    B, NL = logits.shape
+    dev = logits.device
+    if acc.dtype != torch.int64 or acc.numel() != 2 + NL * NL or not acc.is_contiguous() or acc.device != dev:
+        raise _lib.FmmtError(f"eval_accumulate_at: acc must be a contiguous int64 CUDA tensor of {2 + NL * NL} words")
+    if not torch.is_tensor(cursor) or cursor.dtype != torch.int64 or cursor.numel() != 1 or cursor.device != dev:
+        raise _lib.FmmtError("eval_accumulate_at: cursor must be an int64 tensor of one word on the logits' device")
+    if (not torch.is_tensor(logits_out) or logits_out.dtype != torch.float32 or logits_out.dim() != 2 or logits_out.shape[1] != NL
+            or not logits_out.is_contiguous() or logits_out.device != dev):
+        raise _lib.FmmtError("eval_accumulate_at: logits_out must be a contiguous fp32 (capacity, NL) tensor on the logits' device")
+    cap = logits_out.shape[0]
+    for name, t, dt in (("labels_out", labels_out, torch.int64), ("pred_out", pred_out, torch.int32)):
+        if t is None and name == "pred_out":
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (cap,) or not t.is_contiguous() or t.device != dev:
+            raise _lib.FmmtError(f"eval_accumulate_at: {name} must be a contiguous {dt} ({cap},) tensor on the logits' device (logits_out's rows)")
+    lg = logits.detach()
+    if lg.stride(1) != 1:
+        lg = lg.contiguous()
+    lab = labels.detach().to(device=dev, dtype=torch.int64).contiguous()
+    a = acc.data_ptr()
+    check(_lib.load().fmmt_eval_accumulate_at(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), a, a + 8, a + 16, _p(cursor), _p(logits_out),
+                                              _p(labels_out), _p(pred_out), int(cap), _st()), f"fmmt_eval_accumulate_at(B={B},NL={NL},capacity={cap})")
+
+
 # ------------------------------------------------------------------------------------------------
 # additive-attention pooling -> dropout -> classifier -> cross-entropy (csrc/pool_head.hip)
 # ------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ Registered (forward ops return what their backward needs as extra outputs, as cu
                        -> (y, xn, attn_out, mean, rstd, lse)                               norm1 -> (S)W-MSA -> proj -> residual (C = 96: one launch; 192: four), recompute backward
     fmmt::emotion_head(feats, w1, b1, w2, b2, gumbel?, tau) -> (preds, importance)         evaluation: Swin's target-task head + Gumbel-softmax + importance (no gradient)
     fmmt::eval_accumulate(logits, labels, acc!, logits_out!?, out_offset) -> pred           evaluation: loss sum / count / confusion matrix accumulated on the device (no gradient)
+    fmmt::eval_accumulate_at(logits, labels, acc!, cursor!, logits_out!, labels_out!, pred_out!?) -> ()   the same update, the batch's rows kept at a device-held row index that it advances
 
 The nn.Modules of facialmmt_amd/modules keep using ops.py (fewer dispatcher hops per launch); tests/test_gpu_torch_ops.py
 holds the two front ends bit-identical, forward and backward, and runs torch.library.opcheck on each operator."""
@@ -533,3 +534,13 @@ def eval_accumulate(logits: Tensor, labels: Tensor, acc: Tensor, logits_out: Opt
 @eval_accumulate.register_fake
 def _(logits, labels, acc, logits_out, out_offset):
     return logits.new_empty(logits.shape[0], dtype=torch.int32)
+
+
+@torch.library.custom_op(f"{_LIB}::eval_accumulate_at", mutates_args=("acc", "cursor", "logits_out", "labels_out", "pred_out"), device_types="cuda")
+def eval_accumulate_at(logits: Tensor, labels: Tensor, acc: Tensor, cursor: Tensor, logits_out: Tensor, labels_out: Tensor, pred_out: Optional[Tensor]) -> None:
+    ops.eval_accumulate_at(logits, labels, acc, cursor, logits_out, labels_out, pred_out)
+
+
+@eval_accumulate_at.register_fake
+def _(logits, labels, acc, cursor, logits_out, labels_out, pred_out):
+    return None

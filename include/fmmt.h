@@ -516,6 +516,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_pool_head.h"
 /* Ragged frame counts behind one captured shape (device-side packing, the row-masked BatchNorm1d, the frame filter's n_valid): likewise, held to _lib.RAGGED_SIGNATURES. */
 #include "fmmt_ragged.h"
+/* The metric update that collects a split's logits and labels at a device-held row index (fmmt_eval_accumulate_at): likewise, held to _lib.EVAL_COLLECT_SIGNATURES. */
+#include "fmmt_eval_collect.h"
 
 #ifdef __cplusplus
 }
