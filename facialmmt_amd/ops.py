@@ -1702,11 +1702,12 @@ def _n_valid_word(n_valid, device, what):
     return n_valid
 
 
-def pack_frames(frames, num_imgs, capacity):
+def pack_frames(frames, num_imgs, capacity, counts=None):
     """(B, Lv, ...) frames as the loader pads them + num_imgs (B,) -> (packed (capacity, ...), counts): the real frames in the reference's
     concatenation order (train.py:60-71: torch.cat([frames[u, :n_u] for u])) at the front, zeros behind, in ONE launch without a host
     synchronisation (fmmt_pack_frames).  counts: int32 (2,) on the device, [min(total, capacity), total]; counts is what the n_valid arguments of
-    batch_norm_1d / select_frames take.  Frames behind `capacity` are dropped (counts[1] > capacity).  Any dtype whose row is a multiple of 16 bytes."""
+    batch_norm_1d / select_frames take.  Frames behind `capacity` are dropped (counts[1] > capacity).  Any dtype whose row is a multiple of 16 bytes.
+    `counts` (None: a new tensor): the contiguous int32 (2,) device tensor the kernel writes into -- several captured graphs then share one."""
     _need_cuda(frames, "pack_frames")
     if frames.dim() < 3:
         raise ValueError(f"pack_frames expects (B, Lv, ...) frames, got {tuple(frames.shape)}")
@@ -1718,7 +1719,10 @@ def pack_frames(frames, num_imgs, capacity):
         raise ValueError(f"pack_frames: num_imgs must hold one count per utterance ({B}), got {tuple(n.shape)}")
     capacity = int(capacity)
     packed = torch.empty((max(capacity, 0),) + tuple(f.shape[2:]), dtype=f.dtype, device=f.device)
-    counts = torch.empty(2, dtype=torch.int32, device=f.device)
+    if counts is None:
+        counts = torch.empty(2, dtype=torch.int32, device=f.device)
+    elif counts.dtype != torch.int32 or tuple(counts.shape) != (2,) or counts.device != f.device or not counts.is_contiguous():
+        raise ValueError("pack_frames: counts must be a contiguous int32 (2,) tensor on the frames' device")
     check(_lib.load().fmmt_pack_frames(B, Lv, capacity, row_bytes, _p(f), _p(n), _p(packed), _p(counts), _st()),
           f"fmmt_pack_frames(B={B},Lv={Lv},capacity={capacity},row_bytes={row_bytes})")
     return packed, counts

@@ -82,6 +82,25 @@ def check_frame_total(num_imgs, Lv, capacity):
         raise ValueError(f"the batch holds {total} face frames, the step was built for frame_capacity={capacity}")
 
 
+def frame_buckets(frame_capacity):
+    """`frame_capacity` as the steps take it -> the ascending tuple of capacities ("buckets"), or None.  None -> None; an integer c -> (c,); a
+    tuple or list must be non-empty, positive, ascending and free of duplicates.  Anything else: ValueError.  Pure host code."""
+    if frame_capacity is None:
+        return None
+    caps = tuple(int(c) for c in frame_capacity) if isinstance(frame_capacity, (tuple, list)) else (int(frame_capacity),)
+    if not caps or caps[0] < 1 or any(a >= b for a, b in zip(caps, caps[1:])):
+        raise ValueError(f"frame_capacity: a positive number of frames, or an ascending tuple of them without duplicates, got {frame_capacity!r}")
+    return caps
+
+
+def frame_bucket(num_imgs, Lv, capacities):
+    """The capacity a training step runs a ragged batch in: eval_step.pick_bucket's rule, not a second statement of it (the smallest capacity that
+    holds sum(clamp(num_imgs, 0, Lv)) for a list or CPU tensor, ValueError naming the largest when none does; the largest for a device tensor).
+    Imported on the call: eval_step imports this module."""
+    from .eval_step import pick_bucket
+    return pick_bucket(num_imgs, Lv, capacities)
+
+
 def pick_concurrent_stream(device, candidates: int = 8, cycles: int = 4_000_000):
     """A HIP stream that really runs concurrently with the current one.  HIP multiplexes streams onto a handful of
     hardware queues (4 by default) and two streams that share a queue serialise; which queue a new stream lands on
@@ -258,8 +277,12 @@ class TargetStep:
         `discarded_swin_gradients`: "compute" (default, what the reference executes) or "skip" -- see SKIP_NOTE.
         `frame_capacity` (None: `frames` is the compact (sum num_imgs, ...) tensor): the batch carries `frames` as the loader pads them,
         (B, Lv, ...), and the step packs them on the device into `frame_capacity` rows (ops.pack_frames), runs Swin on all of them with the
-        head's BatchNorm over the real ones and filters with the same row count -- GraphedTargetStep(frame_capacity=...) launch by launch."""
-        self.frame_capacity = None if frame_capacity is None else int(frame_capacity)
+        head's BatchNorm over the real ones and filters with the same row count -- GraphedTargetStep(frame_capacity=...) launch by launch.  An
+        ascending tuple of capacities: every batch is packed into the smallest that holds it (`frame_bucket`: num_imgs as a list or CPU tensor; a
+        device tensor takes the largest); `capacity` is the one the last call ran in, `replays` counts the calls per capacity."""
+        self.capacities = frame_buckets(frame_capacity)
+        self.frame_capacity = None if self.capacities is None else self.capacities[-1]
+        self.capacity, self.replays = None, {c: 0 for c in self.capacities or ()}
         self.frame_counts = None                             # packed path: ops.pack_frames' counts of the last step (device, int32 [n_valid, total])
         if discarded_swin_gradients not in ("compute", "skip"):
             raise ValueError("discarded_swin_gradients: 'compute' or 'skip'")
@@ -306,12 +329,14 @@ class TargetStep:
             mark("start")
         from .parallel import GradientAverager, accumulate
         n_valid, swin_kw = None, {}
-        if self.frame_capacity is not None:
-            check_frame_total(num_imgs, frames.shape[1], self.frame_capacity)
+        if self.capacities is not None:
+            cap = frame_bucket(num_imgs, frames.shape[1], self.capacities)     # ValueError before anything is launched
             from . import ops
             num_imgs = torch.as_tensor(num_imgs).to(frames.device)
-            frames, n_valid = ops.pack_frames(frames, num_imgs, self.frame_capacity)
+            frames, n_valid = ops.pack_frames(frames, num_imgs, cap)
             self.frame_counts, swin_kw = n_valid, {"n_valid": n_valid}
+            self.capacity = cap
+            self.replays[cap] += 1
         self.i_batch += 1
         last = self.i_batch % args.trg_accumulation_steps == 0
         if getattr(self.mm, "text_stream", None) is not None:
@@ -881,13 +906,14 @@ class FusedHandOver:
     contiguous fp32 / bf16 tensor: the caller then takes the two-pass path.  The tables are built from the gradients' addresses on every call
     (warm-up passes, then once under capture: a captured step replays the copy of the one pinned table made then)."""
 
-    def __init__(self, n_records: int):
+    def __init__(self, n_records: int, captures: int = 4):
         # pinned host tables, allocated HERE (a host allocation is illegal while a stream captures): two, used alternately -- an eager
         # (warm-up) call waits for the stream before it rewrites one, the call under capture leaves its table untouched for the replays
         self.hosts = [torch.empty(32 * max(1, n_records), dtype=torch.uint8).pin_memory() for _ in range(2)]
         # a call UNDER CAPTURE gets a table of its own that no later call rewrites (the captured copy node re-reads it on every replay: an
-        # eager call after the capture -- a re-capture, a debugging pass -- must not land in it); four captures per object, then it raises
-        self.capture_hosts = [torch.empty(32 * max(1, n_records), dtype=torch.uint8).pin_memory() for _ in range(4)]
+        # eager call after the capture -- a re-capture, a debugging pass -- must not land in it); `captures` (four) captures per object, then it raises.
+        # A step with several frame capacities captures its forward/backward once per capacity: one table each, the records' destinations the same
+        self.capture_hosts = [torch.empty(32 * max(1, n_records), dtype=torch.uint8).pin_memory() for _ in range(max(1, int(captures)))]
         self.captures = 0
         self.calls = 0
         self.keep = []                                       # (device table, partial sums): alive as long as the graphs
@@ -1111,7 +1137,16 @@ class GraphedTargetStep:
         the count in a device word) -> Swin on all F_cap rows with the head's BatchNorm over the real ones -> the frame filter with the same count.
         num_imgs as a list or CPU tensor (the reference's collate) is checked against F_cap on the host (ValueError); a device tensor is the
         caller's contract and `frame_counts` (int32 [n_valid, total], device) is there for a check at the end of an epoch.  Default single-graph
-        mode only: NotImplementedError together with pipeline_swin / branch_graphs / fork_streams / an active averager."""
+        mode only: NotImplementedError together with pipeline_swin / branch_graphs / fork_streams / an active averager.
+        An ascending tuple (c_1 < ... < c_k) ("buckets", `frame_buckets`) captures the forward/backward graph once per capacity -- pack into c_i rows,
+        Swin on c_i rows, everything behind it as above -- and a call replays the smallest that holds its batch (`frame_bucket`: num_imgs on the
+        host; more frames than c_k: ValueError before any copy or launch; a device tensor replays c_k unread).  The captures share the static
+        inputs, the flat gradient buffers with the hand-over's destinations, graph B, the optimizer state and learning-rate word, the bf16
+        shadows, the generator and `frame_counts`, so an accumulation window may mix capacities; each keeps its saved activations in a memory pool
+        of its own (BUCKET_NOTE).  A capacity below the sample batch's total is warmed up and captured on the sample's counts cut down to fit, and
+        every warm-up is undone as the single one is.  `capacities`: the tuple; `capacity`: the last call's; `replays`: {capacity: calls};
+        `capture_bytes` / `capture_reserved_bytes`: {capacity: growth of torch.cuda.memory_allocated / memory_reserved over its capture} (the
+        saved activations are free blocks of the capture's private pool once it ends: the reserved figure is the memory a capacity costs)."""
         import os
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
@@ -1120,15 +1155,19 @@ class GraphedTargetStep:
         self.pipeline = bool(pipeline_swin)
         self.branches = bool(branch_graphs)                 # BRANCH_NOTE below
         self.forked = bool(fork_streams)                    # FORK_NOTE at _fwd_bwd_forked
-        self.frame_capacity = None if frame_capacity is None else int(frame_capacity)
+        self.capacities = frame_buckets(frame_capacity)    # None, (F_cap,) or the ascending buckets: ValueError before anything touches the GPU
+        self.frame_capacity = None if self.capacities is None else self.capacities[-1]
         self.frame_counts = None
+        self.capacity, self.replays, self.capture_bytes, self.capture_reserved_bytes = None, {c: 0 for c in self.capacities or ()}, {}, {}
+        self._cap = self.frame_capacity                     # the capacity the pass in progress (warm-up, capture) packs into
         if self.frame_capacity is not None:
             if self.pipeline or self.branches or self.forked or bool(getattr(averager, "active", False)):
                 raise NotImplementedError("frame_capacity: the default single-graph mode on one rank (not with pipeline_swin / branch_graphs / "
                                           "fork_streams / an active gradient exchange)")
-            if self.frame_capacity < 1 or batch[8].dim() < 3:
+            if batch[8].dim() < 3:
                 raise ValueError("frame_capacity: a positive number of frames, and `frames` as the loader pads them, (B, Lv, ...)")
             check_frame_total(batch[9], batch[8].shape[1], self.frame_capacity)
+        multi = self.capacities is not None and len(self.capacities) > 1
         if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0":
             raise RuntimeError("GraphedTargetStep: DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in the environment before the HIP "
                                "runtime initialises (see facialmmt_amd/__init__.py)")
@@ -1156,7 +1195,7 @@ class GraphedTargetStep:
         # hand-over and clip norm in one pass; with an exchange between the hand-over and the update (N > 1) the hand-over still runs as one pass, its norm is
         # discarded and FusedClipAdamW.update takes the norm of the REDUCED buffers in one more launch
         self.exchanging = bool(getattr(self.flat, "active", False))
-        self.handover = FusedHandOver(len(self.pairs)) if (self.fused is not None and FUSED_HANDOVER) else None
+        self.handover = FusedHandOver(len(self.pairs), captures=max(4, len(self.capacities or ()))) if (self.fused is not None and FUSED_HANDOVER) else None
         self.accumulate = args.trg_accumulation_steps > 1
         self.mm.text_stream = None
         # inside ONE graph the fork / join below become parallel branches; which hardware queue the branches replay on is the
@@ -1176,21 +1215,28 @@ class GraphedTargetStep:
         if masters is not None:
             snap += [(t, t.detach().clone()) for t in masters.masters]
         rng = torch.cuda.get_rng_state(dev)
-        cap.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cap):
-            for _ in range(warmup_iters):
-                self._fwd_bwd()
-                self._update()
-            self.swin.zero_grad(set_to_none=True)
-        torch.cuda.current_stream().wait_stream(cap)
-        torch.cuda.synchronize(dev)
-        _restore(snap)
+        # several capacities: ONE counts word for all captures, and every capacity gets its own warm-up passes (lazy initialisations are per shape) on
+        # the sample's counts cut down to fit it (eval_step._clamp_counts) -- no shape of a pass depends on the counts, only on `_cap`.  After EACH
+        # capacity's passes everything they touched is put back, as the single-capacity constructor does it
+        self._counts_buf = torch.empty(2, dtype=torch.int32, device=dev) if multi else None
+        for c in self.capacities or (None,):
+            if multi:
+                self._use_capacity(c, batch)
+            cap.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(cap):
+                for _ in range(warmup_iters):
+                    self._fwd_bwd()
+                    self._update()
+                self.swin.zero_grad(set_to_none=True)
+            torch.cuda.current_stream().wait_stream(cap)
+            torch.cuda.synchronize(dev)
+            _restore(snap)
+            _reset_optimizer_state(self.opt)
+            if self.fused is not None:
+                self.fused.reset()
+            self.flat.zero_grad()
+            torch.cuda.set_rng_state(rng, dev)
         del snap
-        _reset_optimizer_state(self.opt)
-        if self.fused is not None:
-            self.fused.reset()
-        self.flat.zero_grad()
-        torch.cuda.set_rng_state(rng, dev)
         # -- capture
         self.shadows = _pin_shadows([self.swin, self.mm])
         self.swin_shadows = self.mm_shadows = None
@@ -1210,6 +1256,7 @@ class GraphedTargetStep:
             raise ValueError("fork_streams: one rank without a gradient exchange, Swin's backward computed, not together with pipeline_swin / branch_graphs")
         self.graph_a, self.graph_a2, self.graph_b = torch.cuda.CUDAGraph(), (torch.cuda.CUDAGraph() if self.split else None), torch.cuda.CUDAGraph()
         self.sets, self.side_stream, self.cur, self.prefetched = [], None, 0, None
+        self._graphs = {}                                   # several capacities: capacity -> (graph A, its loss, its kept-frame mask)
         if self.pipeline:
             # two sets (graph S: Swin forward; graph A': everything else), each in a memory pool of ITS OWN: S of one set replays beside A' of the
             # other, and inside a shared pool the capture of the second set would reuse blocks the first set's backward freed
@@ -1269,12 +1316,41 @@ class GraphedTargetStep:
                 with torch.cuda.graph(self.graph_a2, pool=self.graph_a.pool(), stream=cap):
                     self._bwd_swin(swin_out)
                 del swin_out
+            elif multi:
+                # BUCKET_NOTE.  One graph A per capacity, each in a memory pool of ITS OWN: a graph keeps its saved activations in its pool between
+                # its forward and its backward, and graphs that replay in an order the batches decide must not hand each other's blocks out.
+                # Shared, because every capture addresses the same objects: the static inputs, the flat gradient buffers and the hand-over's
+                # destinations, the shadows, the generator, the counts word -- and graph B, which reads none of a graph A's pool (the gradients
+                # have left it through the hand-over) and therefore runs behind whichever A ran; it gets a pool of its own as well
+                for c in self.capacities:
+                    self._use_capacity(c, batch)
+                    g = self.graph_a if c == self.capacities[-1] else torch.cuda.CUDAGraph()
+                    before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
+                    with torch.cuda.graph(g, stream=cap):
+                        loss, new_mask = self._fwd_bwd()
+                    self.capture_bytes[c] = torch.cuda.memory_allocated(dev) - before[0]
+                    self.capture_reserved_bytes[c] = torch.cuda.memory_reserved(dev) - before[1]
+                    self._graphs[c] = (g, loss, new_mask)
+                    _KEEP_GRAPHS.append((g,))
+                    # every capture starts, as the single one does, without Swin gradients: left in place, the next capture's backward would ADD
+                    # into them -- ~170 more launches per replay, writing into this capture's pool
+                    self.swin.zero_grad(set_to_none=True)
+                self.loss, self.new_mask = loss, new_mask
+                with torch.cuda.graph(self.graph_b, stream=cap):
+                    self._update()
             else:
+                before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
                 with torch.cuda.graph(self.graph_a, stream=cap):
                     self.loss, self.new_mask = self._fwd_bwd()
-            with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
-                self._update()
+                if self.frame_capacity is not None:
+                    self.capture_bytes[self.frame_capacity] = torch.cuda.memory_allocated(dev) - before[0]
+                    self.capture_reserved_bytes[self.frame_capacity] = torch.cuda.memory_reserved(dev) - before[1]
+            if not multi:
+                with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
+                    self._update()
         _KEEP_GRAPHS.append((self.graph_a, self.graph_a2, self.graph_b))
+        if multi:
+            self._use_capacity(self.capacities[-1], batch)  # the sample's own counts (they fit the largest capacity) back in the static input
         self.swin.zero_grad(set_to_none=True)              # drop the references; the graph's pool keeps the buffers
         self.mm.pair_stream = None
         self.flat.zero_grad()                              # the capture itself executes nothing
@@ -1417,8 +1493,15 @@ class GraphedTargetStep:
         if self.frame_capacity is None:
             return self.swin(frames, is_trg_task=True)
         from . import ops
-        packed, self.frame_counts = ops.pack_frames(frames, num_imgs, self.frame_capacity)
+        packed, self.frame_counts = ops.pack_frames(frames, num_imgs, self._cap, counts=self._counts_buf)
         return self.swin(packed, is_trg_task=True, n_valid=self.frame_counts)
+
+    def _use_capacity(self, c, batch):
+        """several capacities: the next warm-up / capture packs into `c`, on the sample batch's counts cut down to fit it"""
+        from .eval_step import _clamp_counts
+        self._cap = c
+        with torch.no_grad():
+            self.static[9].copy_(torch.as_tensor(_clamp_counts(batch[9], batch[8].shape[1], c)))
 
     def _swin_forward(self, frames):
         """pipeline_swin, graph S: Swin's forward alone (its bf16 shadows refreshed at the head: an auxiliary step may have moved the weights)"""
@@ -1628,8 +1711,12 @@ class GraphedTargetStep:
             return self._call_pipelined(batch, next_batch)
         if self.branches:
             return self._call_branches(batch)
-        if self.frame_capacity is not None:
-            check_frame_total(batch[9], self.static[8].shape[1], self.frame_capacity)
+        graph_a = self.graph_a
+        if self.capacities is not None:
+            # the smallest capacity that holds the batch (host counts; a device tensor: the largest, unread); ValueError before any copy or launch
+            c = frame_bucket(batch[9], self.static[8].shape[1], self.capacities)
+            if self._graphs:
+                graph_a = self._graphs[c][0]
         with torch.no_grad():
             for i, (dst, src) in enumerate(zip(self.static, batch)):
                 if dst is src:
@@ -1638,7 +1725,12 @@ class GraphedTargetStep:
                 if tuple(src.shape) != tuple(dst.shape):
                     raise ValueError(f"GraphedTargetStep: batch entry {i} has shape {tuple(src.shape)}, the captured graphs are for {tuple(dst.shape)}")
                 dst.copy_(src, non_blocking=True)
-        self.graph_a.replay()
+        graph_a.replay()
+        if self.capacities is not None:
+            self.capacity = c
+            self.replays[c] += 1
+            if self._graphs:
+                _, self.loss, self.new_mask = self._graphs[c]   # every graph A has its own outputs
         self.i_batch += 1
         last = self.i_batch % self.args.trg_accumulation_steps == 0
         if last:
