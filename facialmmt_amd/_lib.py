@@ -109,6 +109,13 @@ EVAL_COLLECT_SIGNATURES = {
     "fmmt_eval_accumulate_at": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int64, _p]),
 }
 
+# include/fmmt_pool_head_rows.h, one to one: a fifth table and header for the same reason -- the pooling head's pair with the row count added behind
+# `keep` (tests/test_pad_rows_cpu.py::test_pool_head_rows_header_signatures_and_library_agree holds table, header and library together)
+POOL_HEAD_ROWS_SIGNATURES = {
+    "fmmt_pool_head_fwd_rows": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _u64, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "fmmt_pool_head_bwd_rows": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+}
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -129,7 +136,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

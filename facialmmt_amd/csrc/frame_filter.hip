@@ -6,7 +6,7 @@
 // train_step.select_frames restates that without host synchronisation as ~55 torch launches (cumsum / searchsorted / index_put / where ...), each a
 // 5 us link in the chain between Swin's forward and the fusion stack.  This file is the same index arithmetic in one kernel:
 //   * every workgroup recomputes the (tiny) index maps in LDS -- selection flags, their inclusive prefix sum, the utterance boundaries with the
-//     reference's (n - 1) margin quirk: utterance u owns the faces [b_{u-1}, b_u) with b_u = sum_{i<=u} n_i - u -- and then writes its share of the
+//     reference's (n - 1) margin quirk: utterance u owns the faces [b_{u-1}, b_u) with b_u = max_{j<=u} (sum_{i<=j} n_i - j) -- and then writes its share of the
 //     (B, Lv, D + NL) output rows;
 //   * `src_face` (B, Lv) records which face fed the emotion columns of a slot (-1: none): the backward is a gather of d(out)[..., D:] through it.
 // Requirements (FMMT_EINVAL otherwise): nF <= 8192 faces, B <= 256, B * Lv <= 8192 slots; num_imgs[u] <= Lv is the caller's contract (the torch
@@ -28,8 +28,8 @@ __global__ __launch_bounds__(FF_THREADS) void select_frames_fwd_kernel(int nF, i
     int* cum = reinterpret_cast<int*>(smem);                  // [nF]   inclusive prefix sum of `owned`
     int* slot = cum + nF;                                     // [B*Lv] face feeding the slot (selection branch), -1 = empty
     int* upper = slot + B * Lv;                               // [B]    exclusive upper face index of utterance u
-    int* nimg = upper + B;                                    // [B]
-    int* before = nimg + B;                                   // [B]    owned faces in front of utterance u
+    int* marg = upper + B;                                    // [B]    the reference's margin of utterance u: sum_{i<u} (n_i - 1)
+    int* before = marg + B;                                   // [B]    owned faces in front of utterance u
     int* run = before + B;                                    // [B]    leading run of ones of vision_mask[u] (fallback branch)
     int* offs = run + B;                                      // [B]    faces in front of utterance u in the fallback enumeration
     int* part = offs + B;                                     // [FF_THREADS] scan partials
@@ -38,12 +38,16 @@ __global__ __launch_bounds__(FF_THREADS) void select_frames_fwd_kernel(int nF, i
     if (tid == 0) {
         n_sel = 0;
         n_real = n_valid ? min(*n_valid, nF) : nF;              // rows behind it are padding of a fixed-capacity batch (ragged.hip): read once per workgroup
-        long long c = 0;
+        long long c = 0, top = 0;
         for (int u = 0; u < B; ++u) {
             const long long n = num_imgs[u];
             c += n;
-            nimg[u] = (int)n;
-            upper[u] = (int)(c - u);
+            marg[u] = (int)(c - u - n);
+            // the reference's loop hands the selected faces out in order: utterance u takes what is left below sum_{i<=u} n_i - u, i.e. the faces from the
+            // largest boundary so far up to its own.  With every n_i >= 1 the boundaries ascend and the running maximum is the boundary itself; an
+            // utterance WITHOUT frames (the padded rows of a short batch: num_imgs = 0) lowers it by one and then owns nothing, as in the loop
+            top = c - u > top ? c - u : top;
+            upper[u] = (int)top;
         }
     }
     for (int i = tid; i < B * Lv; i += FF_THREADS) slot[i] = -1;
@@ -111,7 +115,7 @@ __global__ __launch_bounds__(FF_THREADS) void select_frames_fwd_kernel(int nF, i
         bool keep_in;
         if (any_sel) {
             face = slot[r];
-            const int margin = upper[u] - nimg[u];
+            const int margin = marg[u];
             vrow = face >= 0 ? min(max(face - margin, 0), Lv - 1) : -1;
             keep_in = face >= 0;
             const int first = min(u == 0 ? 0 : upper[u - 1], nF), lastf = min(upper[u], nF);

@@ -18,6 +18,9 @@
 //               tokens -> the four waves in LDS in wave order -> one partial row per workgroup.
 //   backward 2: grid H / 64: a thread per channel adds the B NS partials in their order (d(qq), d(v)) and forms dW = d(logits)^T (keep * pooled); workgroup 0 also
 //               d(b) and d(v_b).  Fixed order throughout: two runs give the same bits.
+// The _rows entry points (include/fmmt_pool_head_rows.h) run the SAME four kernels with a divisor source: n_rows != NULL makes the forward's finishing launch count
+// the rows whose label lies in [0, NL), store the count and divide by it, and makes the backward read that word on the device instead of dividing by B.
+// n_rows == NULL is the B-divisor pair.  Every label valid: count == B, the same division, the same bits.
 // FMMT_BF16: h / ph / dh / dph bf16, everything else and all arithmetic fp32;  FMMT_F32: the same template, nothing rounded.
 #include "fmmt_common.h"
 #include "../../include/fmmt.h"
@@ -165,7 +168,8 @@ __global__ __launch_bounds__(PH_FIN_WAVES * 64) void ph_fwd_finish_kernel(int B,
                                                                           const float* __restrict__ bias, const long long* __restrict__ labels, float p,
                                                                           unsigned long long seed_i, const unsigned long long* __restrict__ seed_ptr,
                                                                           float* __restrict__ alpha, float* __restrict__ pooled, float* __restrict__ keep,
-                                                                          float* __restrict__ logits, float* __restrict__ loss) {
+                                                                          float* __restrict__ logits, float* __restrict__ loss,
+                                                                          int* __restrict__ n_rows) {
     constexpr int KMAX = PH_MAXH / 64;
     __shared__ float rl[PH_MAXB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -244,7 +248,24 @@ __global__ __launch_bounds__(PH_FIN_WAVES * 64) void ph_fwd_finish_kernel(int B,
 #pragma unroll
         for (int k = 0; k < PH_MAXB / 64; ++k) a += rl[lane + 64 * k];
         a = ph_wave_sum(a);
-        if (lane == 0) loss[0] = a / (float)B;
+        if (n_rows == nullptr) {
+            if (lane == 0) loss[0] = a / (float)B;
+        } else {                                            // the mean over the rows that have a label: counted here, in floats (exact: B <= 1024)
+            float c = 0.f;
+#pragma unroll
+            for (int k = 0; k < PH_MAXB / 64; ++k) {
+                const int b = lane + 64 * k;
+                if (b < B) {
+                    const long long label = labels[b];
+                    c += label >= 0 && label < NL ? 1.f : 0.f;
+                }
+            }
+            c = ph_wave_sum(c);
+            if (lane == 0) {
+                n_rows[0] = (int)c;                         // an ordinary vector store
+                loss[0] = c > 0.f ? a / c : 0.f;
+            }
+        }
     }
 }
 
@@ -255,7 +276,7 @@ __global__ __launch_bounds__(PH_THREADS) void ph_bwd_token_kernel(int B, int L, 
                                                                   const float* __restrict__ logits, const float* __restrict__ alpha,
                                                                   const float* __restrict__ pooled, const float* __restrict__ keep, T* __restrict__ dh,
                                                                   T* __restrict__ dph, float* __restrict__ pq, float* __restrict__ pv, float* __restrict__ pvb,
-                                                                  float* __restrict__ dlg) {
+                                                                  float* __restrict__ dlg, const int* __restrict__ n_rows) {
     constexpr int VN = Vec<T>::N, JMAX = PH_MAXH / (VN * 64);
     __shared__ float sdp[PH_MAXH];
     __shared__ float sq[PH_WAVES][PH_MAXH], sv[PH_WAVES][PH_MAXH];
@@ -263,7 +284,7 @@ __global__ __launch_bounds__(PH_THREADS) void ph_bwd_token_kernel(int B, int L, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.x, b = blockIdx.y;
     const int HV = H / VN;
-    // d(logits) of the row: dloss / B * (softmax - onehot)
+    // d(logits) of the row: dloss / B * (softmax - onehot); n_rows: dloss / (rows that have a label), 0 when there is none
     float dl[PH_MAXNL], mx = -INFINITY;
 #pragma unroll
     for (int n = 0; n < PH_MAXNL; ++n) {
@@ -276,7 +297,8 @@ __global__ __launch_bounds__(PH_THREADS) void ph_bwd_token_kernel(int B, int L, 
         dl[n] = n < NL ? expf(dl[n] - mx) : 0.f;
         z += dl[n];
     }
-    const float g = dloss[0] / (float)B;
+    const int nr = n_rows == nullptr ? B : n_rows[0];
+    const float g = nr > 0 ? dloss[0] / (float)nr : 0.f;
     const long long label = labels[b];
 #pragma unroll
     for (int n = 0; n < PH_MAXNL; ++n) {
@@ -438,10 +460,12 @@ extern "C" size_t fmmt_pool_head_bwd_workspace(int B, int L, int H) {
     return ph_round(np * H * 4) * 2 + ph_round(np * 4) + ph_round((size_t)B * PH_MAXNL * 4);
 }
 
-extern "C" int fmmt_pool_head_fwd(int dtype, int B, int L, int H, int NL, const void* h, const void* ph, const float* qq, const float* value_w,
-                                  const float* value_b, const float* mask, const float* cls_w, const float* cls_b, const int64_t* labels, float p, uint64_t seed,
-                                  const uint64_t* seed_dev, float* logits, float* loss, float* alpha, float* pooled, float* keep, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+namespace {
+
+// both forward entry points: n_rows == NULL divides by B, else by the counted rows (stored in n_rows[0])
+int ph_fwd(int dtype, int B, int L, int H, int NL, const void* h, const void* ph, const float* qq, const float* value_w, const float* value_b, const float* mask,
+           const float* cls_w, const float* cls_b, const int64_t* labels, float p, uint64_t seed, const uint64_t* seed_dev, float* logits, float* loss, float* alpha,
+           float* pooled, float* keep, int32_t* n_rows, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
     if (!(p >= 0.f) || !(p < 1.f)) return FMMT_EINVAL;
     if (!h || !ph || !qq || !value_w || !value_b || !mask || !cls_w || !cls_b || !labels || !logits || !loss || !alpha || !pooled || !keep || !workspace) return FMMT_EINVAL;
@@ -462,15 +486,15 @@ extern "C" int fmmt_pool_head_fwd(int dtype, int B, int L, int H, int NL, const 
     FMMT_CHECK_LAUNCH();
     const int nw = B < PH_FIN_WAVES ? B : PH_FIN_WAVES;
     hipLaunchKernelGGL(ph_fwd_finish_kernel, dim3(1), dim3(nw * 64), 0, st, B, L, H, NL, NS, ml, ppool, cls_w, cls_b, (const long long*)labels, p,
-                       (unsigned long long)seed, (const unsigned long long*)seed_dev, alpha, pooled, keep, logits, loss);
+                       (unsigned long long)seed, (const unsigned long long*)seed_dev, alpha, pooled, keep, logits, loss, (int*)n_rows);
     FMMT_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int fmmt_pool_head_bwd(int dtype, int B, int L, int H, int NL, const float* dloss, const void* h, const void* ph, const float* qq,
-                                  const float* value_w, const float* cls_w, const int64_t* labels, const float* logits, const float* alpha, const float* pooled,
-                                  const float* keep, void* dh, void* dph, float* dqq, float* dv, float* dvb, float* dW, float* db, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+// both backward entry points: n_rows == NULL divides by B, else by the device word the forward wrote
+int ph_bwd(int dtype, int B, int L, int H, int NL, const float* dloss, const void* h, const void* ph, const float* qq, const float* value_w, const float* cls_w,
+           const int64_t* labels, const float* logits, const float* alpha, const float* pooled, const float* keep, const int32_t* n_rows, void* dh, void* dph,
+           float* dqq, float* dv, float* dvb, float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
     if (!dloss || !h || !ph || !qq || !value_w || !cls_w || !labels || !logits || !alpha || !pooled || !keep || !dh || !dph || !dqq || !dv || !dvb || !dW || !db ||
         !workspace)
@@ -489,12 +513,51 @@ extern "C" int fmmt_pool_head_bwd(int dtype, int B, int L, int H, int NL, const 
     const dim3 grid(NS, B);
     if (dtype == FMMT_BF16)
         hipLaunchKernelGGL(ph_bwd_token_kernel<bf16>, grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const bf16*)h, (const bf16*)ph, qq, value_w, cls_w,
-                           (const long long*)labels, logits, alpha, pooled, keep, (bf16*)dh, (bf16*)dph, pq, pv, pvb, dlg);
+                           (const long long*)labels, logits, alpha, pooled, keep, (bf16*)dh, (bf16*)dph, pq, pv, pvb, dlg, (const int*)n_rows);
     else
         hipLaunchKernelGGL(ph_bwd_token_kernel<float>, grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const float*)h, (const float*)ph, qq, value_w, cls_w,
-                           (const long long*)labels, logits, alpha, pooled, keep, (float*)dh, (float*)dph, pq, pv, pvb, dlg);
+                           (const long long*)labels, logits, alpha, pooled, keep, (float*)dh, (float*)dph, pq, pv, pvb, dlg, (const int*)n_rows);
     FMMT_CHECK_LAUNCH();
     hipLaunchKernelGGL(ph_bwd_finish_kernel, dim3((H + 63) / 64), dim3(64), 0, st, B, H, NL, NS, pq, pv, pvb, dlg, pooled, keep, dqq, dv, dvb, dW, db);
     FMMT_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int fmmt_pool_head_fwd(int dtype, int B, int L, int H, int NL, const void* h, const void* ph, const float* qq, const float* value_w,
+                                  const float* value_b, const float* mask, const float* cls_w, const float* cls_b, const int64_t* labels, float p, uint64_t seed,
+                                  const uint64_t* seed_dev, float* logits, float* loss, float* alpha, float* pooled, float* keep, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return ph_fwd(dtype, B, L, H, NL, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, seed_dev, logits, loss, alpha, pooled, keep, nullptr, workspace,
+                  workspace_bytes, stream);
+}
+
+extern "C" int fmmt_pool_head_bwd(int dtype, int B, int L, int H, int NL, const float* dloss, const void* h, const void* ph, const float* qq,
+                                  const float* value_w, const float* cls_w, const int64_t* labels, const float* logits, const float* alpha, const float* pooled,
+                                  const float* keep, void* dh, void* dph, float* dqq, float* dv, float* dvb, float* dW, float* db, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return ph_bwd(dtype, B, L, H, NL, dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, nullptr, dh, dph, dqq, dv, dvb, dW, db, workspace,
+                  workspace_bytes, stream);
+}
+
+// the mean over the rows that have a label (include/fmmt_pool_head_rows.h): the same launches, the divisor counted on the device
+extern "C" int fmmt_pool_head_fwd_rows(int dtype, int B, int L, int H, int NL, const void* h, const void* ph, const float* qq, const float* value_w,
+                                       const float* value_b, const float* mask, const float* cls_w, const float* cls_b, const int64_t* labels, float p,
+                                       uint64_t seed, const uint64_t* seed_dev, float* logits, float* loss, float* alpha, float* pooled, float* keep,
+                                       int32_t* n_rows, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;     // the shape first, as the B-divisor pair answers it
+    if (!n_rows) return FMMT_EINVAL;
+    return ph_fwd(dtype, B, L, H, NL, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, seed_dev, logits, loss, alpha, pooled, keep, n_rows, workspace,
+                  workspace_bytes, stream);
+}
+
+extern "C" int fmmt_pool_head_bwd_rows(int dtype, int B, int L, int H, int NL, const float* dloss, const void* h, const void* ph, const float* qq,
+                                       const float* value_w, const float* cls_w, const int64_t* labels, const float* logits, const float* alpha,
+                                       const float* pooled, const float* keep, const int32_t* n_rows, void* dh, void* dph, float* dqq, float* dv, float* dvb,
+                                       float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
+    if (!n_rows) return FMMT_EINVAL;
+    return ph_bwd(dtype, B, L, H, NL, dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, n_rows, dh, dph, dqq, dv, dvb, dW, db, workspace,
+                  workspace_bytes, stream);
 }

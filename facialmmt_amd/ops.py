@@ -1919,10 +1919,11 @@ def _pool_head_args(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels):
     return (B, L, H, NL), _c16(h.detach()), _c16(ph.detach()), f32, lab
 
 
-def pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0):
+def pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0, valid_mean=False):
     """fmmt_pool_head_fwd on tensors (no autograd).  h, ph (B, L, H) bf16 / fp32; the rest as the modules hold them (any shape with the right element
     count, read as fp32); seed: python int or a 1-element int64 CUDA tensor.  Returns (loss (), logits (B, NL), alpha (B, L), pooled (B, H), keep (B, H)),
-    all fp32."""
+    all fp32.  valid_mean: fmmt_pool_head_fwd_rows -- the mean over the rows whose label lies in [0, NL) -- and a sixth result, n_rows (1,) int32, the
+    device word pool_head_bwd_raw takes."""
     (B, L, H, NL), h2, ph2, (q, vw, vb, mk, cw, cb), lab = _pool_head_args(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels)
     dev = h2.device
     lib = _lib.load()
@@ -1934,14 +1935,21 @@ def pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p
     ws = _ws(nbytes, dev)
     seed_t = seed if isinstance(seed, torch.Tensor) else None
     seed_i = 0 if seed_t is not None else int(seed)
+    if valid_mean:
+        n_rows = torch.empty((1,), dtype=torch.int32, device=dev)
+        check(lib.fmmt_pool_head_fwd_rows(dtype_code(h2.dtype), B, L, H, NL, _p(h2), _p(ph2), _p(q), _p(vw), _p(vb), _p(mk), _p(cw), _p(cb), _p(lab), float(p),
+                                          seed_i, _p(seed_t), _p(logits), _p(loss), _p(alpha), _p(pooled), _p(keep), _p(n_rows), _p(ws), nbytes, _st()),
+              f"fmmt_pool_head_fwd_rows(B={B},L={L},H={H},NL={NL})")
+        return loss, logits, alpha, pooled, keep, n_rows
     check(lib.fmmt_pool_head_fwd(dtype_code(h2.dtype), B, L, H, NL, _p(h2), _p(ph2), _p(q), _p(vw), _p(vb), _p(mk), _p(cw), _p(cb), _p(lab), float(p), seed_i,
                                  _p(seed_t), _p(logits), _p(loss), _p(alpha), _p(pooled), _p(keep), _p(ws), nbytes, _st()),
           f"fmmt_pool_head_fwd(B={B},L={L},H={H},NL={NL})")
     return loss, logits, alpha, pooled, keep
 
 
-def pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep):
-    """fmmt_pool_head_bwd on tensors: (dh_pool, dph) in h's dtype, (dqq (H,), dv (H,), dvb (1,), dW (NL, H), db (NL,)) fp32"""
+def pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, n_rows=None):
+    """fmmt_pool_head_bwd on tensors: (dh_pool, dph) in h's dtype, (dqq (H,), dv (H,), dvb (1,), dW (NL, H), db (NL,)) fp32.  n_rows (the int32 device
+    word of pool_head_fwd_raw(..., valid_mean=True)): fmmt_pool_head_bwd_rows, which reads it on the device."""
     B, L, H = h.shape
     NL = cls_w.shape[0]
     dev = h.device
@@ -1955,6 +1963,13 @@ def pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, p
     dW, db = torch.empty((NL, H), dtype=torch.float32, device=dev), torch.empty((NL,), dtype=torch.float32, device=dev)
     nbytes = lib.fmmt_pool_head_bwd_workspace(B, L, H)
     ws = _ws(nbytes, dev)
+    if n_rows is not None:
+        if n_rows.dtype != torch.int32 or n_rows.device != dev or n_rows.numel() < 1:
+            raise _lib.FmmtError(f"pool_head_loss: n_rows must be the int32 word of the forward on {dev}")
+        check(lib.fmmt_pool_head_bwd_rows(dtype_code(h2.dtype), B, L, H, NL, _p(dl), _p(h2), _p(ph2), _p(q), _p(vw), _p(cw), _p(labels), _p(logits), _p(alpha),
+                                          _p(pooled), _p(keep), _p(n_rows), _p(dh), _p(dph), _p(dqq), _p(dv), _p(dvb), _p(dW), _p(db), _p(ws), nbytes, _st()),
+              f"fmmt_pool_head_bwd_rows(B={B},L={L},H={H},NL={NL})")
+        return dh, dph, dqq, dv, dvb, dW, db
     check(lib.fmmt_pool_head_bwd(dtype_code(h2.dtype), B, L, H, NL, _p(dl), _p(h2), _p(ph2), _p(q), _p(vw), _p(cw), _p(labels), _p(logits), _p(alpha), _p(pooled),
                                  _p(keep), _p(dh), _p(dph), _p(dqq), _p(dv), _p(dvb), _p(dW), _p(db), _p(ws), nbytes, _st()),
           f"fmmt_pool_head_bwd(B={B},L={L},H={H},NL={NL})")
@@ -1964,13 +1979,18 @@ def pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, p
 class PoolHeadLossFn(Function):
     """(loss, logits) of the V-only classifier's tail behind ph = P h + b_P and qq = Q query_vector + b_Q (modules/Transformer.py:24-45, src/models.py:219-221,
     train.py:258): two launches forward, two backward (csrc/pool_head.hip).  The gradient flows from the loss; the logits are returned for the caller's
-    bookkeeping and are not differentiable.  Saved: alpha, the pooled vector, the keep mask (the dropout is not replayed: B x H values)."""
+    bookkeeping and are not differentiable.  Saved: alpha, the pooled vector, the keep mask (the dropout is not replayed: B x H values).
+    valid_mean: the fmmt_pool_head_*_rows pair (mean over the labelled rows); the row count stays a device word in the context."""
 
     @staticmethod
-    def forward(ctx, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed):
+    def forward(ctx, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, valid_mean=False):
         _need_cuda(h, "pool_head_loss")
         lab = labels.detach().to(device=h.device, dtype=torch.int64).contiguous()      # once: the raw call below finds it as it needs it
-        loss, logits, alpha, pooled, keep = pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed)
+        if valid_mean:
+            loss, logits, alpha, pooled, keep, ctx.n_rows = pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed, True)
+        else:
+            loss, logits, alpha, pooled, keep = pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed)
+            ctx.n_rows = None
         ctx.save_for_backward(h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep)
         ctx.shapes = (qq.shape, value_w.shape, value_b.shape, cls_w.shape, cls_b.shape)
         ctx.dtypes = (qq.dtype, value_w.dtype, value_b.dtype, cls_w.dtype, cls_b.dtype)
@@ -1980,12 +2000,13 @@ class PoolHeadLossFn(Function):
     @staticmethod
     def backward(ctx, dloss, _dlogits):
         h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep = ctx.saved_tensors
-        dh, dph, dqq, dv, dvb, dW, db = pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep)
+        dh, dph, dqq, dv, dvb, dW, db = pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep, ctx.n_rows)
         sh, dt = ctx.shapes, ctx.dtypes
         outs = [g.reshape(s).to(d) for g, s, d in zip((dqq, dv, dvb, dW, db), sh, dt)]
-        return dh.reshape(h.shape), dph.reshape(h.shape), outs[0], outs[1], outs[2], None, outs[3], outs[4], None, None, None
+        return dh.reshape(h.shape), dph.reshape(h.shape), outs[0], outs[1], outs[2], None, outs[3], outs[4], None, None, None, None
 
 
-def pool_head_loss(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0):
-    """-> (loss, logits): mean cross-entropy of classifier(dropout(additive-attention pooling of h)) and the logits (see PoolHeadLossFn)"""
-    return PoolHeadLossFn.apply(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed)
+def pool_head_loss(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0, valid_mean=False):
+    """-> (loss, logits): mean cross-entropy of classifier(dropout(additive-attention pooling of h)) and the logits (see PoolHeadLossFn).  valid_mean:
+    the mean runs over the rows whose label lies in [0, NL) (F.cross_entropy's ignore_index rule for a padded batch) instead of over all B rows."""
+    return PoolHeadLossFn.apply(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, bool(valid_mean))

@@ -26,7 +26,7 @@ def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold, n_vali
 
     n_valid (a 1-element integer tensor on preds' device, ops.pack_frames' counts; None: every row is a face): preds holds a fixed
     capacity of rows of which the first n_valid are faces.  "No face at all passes" (train.py:80,84) is then decided over those rows
-    only; ownership needs nothing (an owned face lies below sum(num_imgs) - (B - 1) <= n_valid)."""
+    only; ownership needs nothing (an owned face lies below the largest boundary max_u (sum_{i<=u} num_imgs_i - u) <= sum(num_imgs) = n_valid)."""
     B, Lv, D = vision_inputs.shape
     dev = preds.device
     nF = preds.shape[0]
@@ -38,10 +38,13 @@ def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold, n_vali
     importance = (preds * preds).sum(dim=1)                       # == diag(P P^T)
     sel = importance > threshold                                   # (nF,)
     g = torch.arange(nF, device=dev)
-    # utterance boundaries with the reference's (n - 1) margin: b_u = sum_{i<=u} n_i - u
+    # utterance boundaries with the reference's (n - 1) margin: b_u = sum_{i<=u} n_i - u; the loop hands the faces out in order, so an utterance
+    # takes what lies between the largest boundary so far and its own -- the running maximum, which IS b_u while every n_i >= 1 and leaves an
+    # utterance without frames (a padded row of a short batch, pad_target_batch) owning nothing
     csum = torch.cumsum(n, 0)
-    upper = csum - torch.arange(B, device=dev)                     # exclusive upper bound of utterance u
-    margin = upper - n                                             # sum_{i<u}(n_i - 1)
+    raw = csum - torch.arange(B, device=dev)
+    upper = torch.cummax(raw, 0).values                            # exclusive upper bound of utterance u (raw[0] = n_0 >= 0: never negative)
+    margin = raw - n                                               # sum_{i<u}(n_i - 1)
     u = torch.searchsorted(upper, g, right=True)                   # owning utterance (== B: dropped tail)
     owned = sel & (u < B)
     uc = u.clamp(max=B - 1)
@@ -99,6 +102,76 @@ def frame_bucket(num_imgs, Lv, capacities):
     Imported on the call: eval_step imports this module."""
     from .eval_step import pick_bucket
     return pick_bucket(num_imgs, Lv, capacities)
+
+
+# ------------------------------------------------------------------------------------------------
+# A short last batch of an epoch behind a captured batch shape (pad_rows=True on the graphed steps).  PAD_NOTE: the rule for what a padded row
+# holds, stated once.  Every padded row is a computation that can occur for a real utterance -- no kernel meets a degenerate case (a row whose
+# masks are all zero gives NaN in the pooling head's softmax and in the text encoder's attention) -- and its label is -100, F.cross_entropy's
+# default ignore_index: the loss is the mean over the real rows, and a padded row's gradient is zero from the loss on down.
+# ------------------------------------------------------------------------------------------------
+IGNORE_LABEL = -100
+
+
+def _pad_count(b, rows, what):
+    if b < 1 or b > rows:
+        raise ValueError(f"{what}: a batch of {b} rows cannot be padded to {rows} rows (1 <= rows of the batch <= {rows})")
+    return rows - b
+
+
+def _pad_like_row0(t, extra):
+    return torch.cat((t, t[:1].expand(extra, *t.shape[1:])), dim=0)
+
+
+def _pad_const(t, extra, value=0):
+    return torch.cat((t, t.new_full((extra, *t.shape[1:]), value)), dim=0)
+
+
+def pad_target_batch(batch, rows):
+    """The T+A+V batch (ids, attn_mask, sep_mask, audio, audio_mask, vision_inputs, vision_mask, labels, frames, num_imgs, utt_idx) with
+    1 <= b <= rows utterances -> the same batch with `rows` utterances (b == rows: the entries as they are); ValueError otherwise.  A padded row:
+      * ids, attn_mask, sep_mask, audio, audio_mask, utt_idx: COPIES OF ROW 0 -- a valid text and audio row (an all-zero attention mask would be a
+        softmax over nothing);
+      * vision_inputs, vision_mask, frames: ZEROS, num_imgs = 0.  The mask is zero and not copied: the reference's keep-everything branch
+        (train.py:122-130) walks the vision_mask == 1 slots and takes Swin's rows in order, so a copied mask would run past the real frames; zero
+        frames keep the BatchNorm statistics and the "any face passed" count over the real frames (the n_valid path of frame_capacity), and in the
+        selection branch an utterance without frames owns nothing (select_frames: the boundaries as a running maximum);
+      * labels = -100.
+    `frames` is the loader's (b, Lv, ...) tensor; num_imgs and utt_idx may be lists (the reference's collate) or tensors and keep their kind.
+    Works on CPU or device tensors; nothing is launched in-tree."""
+    if len(batch) != 11:
+        raise ValueError(f"pad_target_batch: a batch of 11 entries, got {len(batch)}")
+    extra = _pad_count(len(batch[7]), rows, "pad_target_batch")
+    if extra == 0:
+        return tuple(batch)
+    out = list(batch)
+    for i in (0, 1, 2, 3, 4):
+        out[i] = _pad_like_row0(batch[i], extra)
+    for i in (5, 6, 8):
+        out[i] = _pad_const(batch[i], extra)
+    out[7] = _pad_const(torch.as_tensor(batch[7]), extra, IGNORE_LABEL)
+    out[9] = _pad_const(batch[9], extra) if torch.is_tensor(batch[9]) else list(batch[9]) + [0] * extra
+    out[10] = _pad_like_row0(batch[10], extra) if torch.is_tensor(batch[10]) else list(batch[10]) + [batch[10][0]] * extra
+    return tuple(out)
+
+
+def pad_unimodal_batch(batch, rows):
+    """The V-only batch (feature, mask, labels) with 1 <= b <= rows rows -> `rows` rows: feature and mask of a padded row are copies of row 0 (a row
+    the model already computes: finite everywhere), its label is -100.  b == rows: the entries as they are; b == 0 or b > rows: ValueError."""
+    feature, mask, labels = batch
+    extra = _pad_count(feature.shape[0], rows, "pad_unimodal_batch")
+    if extra == 0:
+        return feature, mask, labels
+    return _pad_like_row0(feature, extra), _pad_like_row0(mask, extra), _pad_const(torch.as_tensor(labels), extra, IGNORE_LABEL)
+
+
+def pad_aux_batch(images, labels, rows):
+    """The auxiliary batch (images, labels) with 1 <= b <= rows images -> `rows` images: a padded image is zeros, its label -100.  The step passes b
+    as the head BatchNorm's n_valid, so the padded rows take no part in the batch statistics and get no gradient."""
+    extra = _pad_count(images.shape[0], rows, "pad_aux_batch")
+    if extra == 0:
+        return images, labels
+    return _pad_const(images, extra), _pad_const(torch.as_tensor(labels), extra, IGNORE_LABEL)
 
 
 def pick_concurrent_stream(device, candidates: int = 8, cycles: int = 4_000_000):
@@ -1118,7 +1191,8 @@ class GraphedTargetStep:
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
-                 swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None):
+                 swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None,
+                 pad_rows: bool = False):
         """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
@@ -1146,7 +1220,14 @@ class GraphedTargetStep:
         of its own (BUCKET_NOTE).  A capacity below the sample batch's total is warmed up and captured on the sample's counts cut down to fit, and
         every warm-up is undone as the single one is.  `capacities`: the tuple; `capacity`: the last call's; `replays`: {capacity: calls};
         `capture_bytes` / `capture_reserved_bytes`: {capacity: growth of torch.cuda.memory_allocated / memory_reserved over its capture} (the
-        saved activations are free blocks of the capture's private pool once it ends: the reserved figure is the memory a capacity costs)."""
+        saved activations are free blocks of the capture's private pool once it ends: the reserved figure is the memory a capacity costs).
+        `pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B utterances whose other dimensions match is
+        padded to the captured B by pad_target_batch (PAD_NOTE) and replayed through the same captures -- same flat buffers, same fused optimizer,
+        same generator; the bucket is chosen from the padded num_imgs, which sum to the real frames; the loss is F.cross_entropy's mean over the
+        real rows (label -100 is its ignore_index).  Nothing captured depends on B other than through shapes the padding keeps fixed: the only
+        cross-row operations are the head's BatchNorm and the filter's "any face passed" (both over the device frame count) and the loss's mean.
+        Needs frame_capacity (compact frames change shape with the batch: ValueError) and the default single-graph mode on one rank
+        (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
         import os
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
@@ -1155,6 +1236,12 @@ class GraphedTargetStep:
         self.pipeline = bool(pipeline_swin)
         self.branches = bool(branch_graphs)                 # BRANCH_NOTE below
         self.forked = bool(fork_streams)                    # FORK_NOTE at _fwd_bwd_forked
+        self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
+        if self.pad_rows and frame_capacity is None:
+            raise ValueError("pad_rows: only with frame_capacity (compact frames change their shape with the batch's rows)")
+        if self.pad_rows and (pipeline_swin or branch_graphs or fork_streams or bool(getattr(averager, "active", False))):
+            raise NotImplementedError("pad_rows: the default single-graph mode on one rank (not with pipeline_swin / branch_graphs / fork_streams / "
+                                      "an active gradient exchange)")
         self.capacities = frame_buckets(frame_capacity)    # None, (F_cap,) or the ascending buckets: ValueError before anything touches the GPU
         self.frame_capacity = None if self.capacities is None else self.capacities[-1]
         self.frame_counts = None
@@ -1711,6 +1798,13 @@ class GraphedTargetStep:
             return self._call_pipelined(batch, next_batch)
         if self.branches:
             return self._call_branches(batch)
+        rows = self.static[7].shape[0]
+        if self.pad_rows:
+            b = len(batch[7])
+            if b != rows:
+                batch = pad_target_batch(batch, rows)       # ValueError for b == 0 or b > rows, before any copy or launch
+        else:
+            b = rows
         graph_a = self.graph_a
         if self.capacities is not None:
             # the smallest capacity that holds the batch (host counts; a device tensor: the largest, unread); ValueError before any copy or launch
@@ -1726,6 +1820,8 @@ class GraphedTargetStep:
                     raise ValueError(f"GraphedTargetStep: batch entry {i} has shape {tuple(src.shape)}, the captured graphs are for {tuple(dst.shape)}")
                 dst.copy_(src, non_blocking=True)
         graph_a.replay()
+        self.rows = b
+        self.padded_calls += int(b != rows)
         if self.capacities is not None:
             self.capacity = c
             self.replays[c] += 1
@@ -1824,10 +1920,16 @@ class GraphedAuxStep:
     """The auxiliary-task step (train.py:15-41: Swin -> logits -> cross-entropy -> backward -> clip -> AdamW on the Swin
     model) as two HIP graphs, same construction as GraphedTargetStep; the Swin gradients are the exchanged ones here."""
 
-    def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2):
+    def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False):
+        """`pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
+        pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
+        device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
+        (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
         from .parallel import GradientAverager
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
         self.images, self.labels = images.clone(), labels.clone()
+        self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
+        self.n_valid = torch.full((1,), images.shape[0], dtype=torch.int32, device=images.device) if self.pad_rows else None
         self.shadows = None
         self.i_batch = 0
         dev = images.device
@@ -1870,7 +1972,10 @@ class GraphedAuxStep:
     def _fwd_bwd(self):
         if self.shadows is not None:
             self.shadows.refresh()
-        loss = self.swin(self.images, False, self.labels, F.cross_entropy) / self.args.aux_accumulation_steps
+        if self.pad_rows:
+            loss = self.swin(self.images, False, self.labels, F.cross_entropy, n_valid=self.n_valid) / self.args.aux_accumulation_steps
+        else:
+            loss = self.swin(self.images, False, self.labels, F.cross_entropy) / self.args.aux_accumulation_steps
         loss.backward()
         if self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm):
             self.fused.norm_ready = not self.exchanging      # N > 1: the norm is taken again over the reduced buffers
@@ -1892,6 +1997,10 @@ class GraphedAuxStep:
             p.grad = None
 
     def __call__(self, images, labels):
+        rows = b = self.images.shape[0]
+        if self.pad_rows and images.dim() == self.images.dim() and images.shape[0] != rows:
+            b = images.shape[0]
+            images, labels = pad_aux_batch(images, labels, rows)     # ValueError for b == 0 or b > rows, before any copy or launch
         if tuple(images.shape) != tuple(self.images.shape) or tuple(labels.shape) != tuple(self.labels.shape):
             raise ValueError(f"GraphedAuxStep: batch of shape {tuple(images.shape)} / {tuple(labels.shape)}, captured for "
                              f"{tuple(self.images.shape)} / {tuple(self.labels.shape)}")
@@ -1899,7 +2008,11 @@ class GraphedAuxStep:
             if images is not self.images:
                 self.images.copy_(images, non_blocking=True)
                 self.labels.copy_(labels, non_blocking=True)
+            if self.n_valid is not None:
+                self.n_valid.fill_(b)                        # a device fill: no host synchronisation
         self.graph_a.replay()
+        self.rows = b
+        self.padded_calls += int(b != rows)
         self.i_batch += 1
         if self.i_batch % self.args.aux_accumulation_steps == 0:
             self.flat.exchange_all()                         # Swin's gradients: 187 MB fp32, nothing left in the step to hide them behind
@@ -1971,15 +2084,22 @@ class GraphedUnimodalStep:
     """UnimodalStep as two HIP graphs, the construction of GraphedAuxStep: graph A = bf16 shadow refresh, forward_loss, backward, gradient hand-over into
     flat fp32 buffers (+ the clip norm); graph B = clip + optimizer step (one fused launch for AdamW / HFAdamW with a device learning rate).  The warm-up
     passes run on a side stream and are undone (parameter snapshot, optimizer state zeroed); the dropout seeds are drawn on the device inside graph A,
-    so every replay draws fresh masks.  The batch shape is the captured one: another shape raises ValueError -- a short last batch of an epoch goes
-    through UnimodalStep on the same model and optimizer."""
+    so every replay draws fresh masks.  The batch shape is the captured one: another shape raises ValueError.  A short last batch of an epoch must NOT
+    go through an eager UnimodalStep on the same model and optimizer: with the fused optimizer on, the moments and the step counter live in
+    FusedClipAdamW and `optimizer.state` is empty, so the eager update would start Adam from zero for that one step and the graphs would continue
+    with moments that never saw it; with trg_accumulation_steps > 1 the eager micro-step accumulates in p.grad, which graph B never reads.
+    `pad_rows=True` is the way: the capture runs forward_loss(..., valid_mean=True) -- the loss is the mean over the rows that have a label, the
+    same bits as the plain loss on a full batch --, and a batch with 1 <= b <= B rows is padded to B by pad_unimodal_batch (copies of row 0, label
+    -100) and replayed through the same graphs, flat buffers and optimizer state; the loss returned is the mean over the b real rows /
+    trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
 
-    def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2):
+    def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False):
         from .parallel import GradientAverager
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
         self.autocast_dtype = autocast_dtype
         feature, mask, labels = batch
         self.feature, self.mask, self.labels = feature.clone(), mask.clone(), torch.as_tensor(labels, device=feature.device).clone()
+        self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
         self.shadows = None
         self.i_batch = 0
         dev = feature.device
@@ -2021,11 +2141,12 @@ class GraphedUnimodalStep:
     def _fwd_bwd(self):
         if self.shadows is not None:
             self.shadows.refresh()
+        kw = {"valid_mean": True} if self.pad_rows else {}
         if self.autocast_dtype is not None:
             with torch.autocast("cuda", dtype=self.autocast_dtype, cache_enabled=False):
-                loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels)
+                loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels, **kw)
         else:
-            loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels)
+            loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels, **kw)
         self.logits = logits.detach()
         loss = loss / self.args.trg_accumulation_steps
         loss.backward()
@@ -2050,6 +2171,10 @@ class GraphedUnimodalStep:
 
     def __call__(self, batch):
         feature, mask, labels = batch
+        rows = b = self.feature.shape[0]
+        if self.pad_rows and feature.dim() == self.feature.dim() and feature.shape[0] != rows:
+            b = feature.shape[0]
+            feature, mask, labels = pad_unimodal_batch(batch, rows)     # ValueError for b == 0 or b > rows, before any copy or launch
         if tuple(feature.shape) != tuple(self.feature.shape) or tuple(mask.shape) != tuple(self.mask.shape) or tuple(labels.shape) != tuple(self.labels.shape):
             raise ValueError(f"GraphedUnimodalStep: batch of shape {tuple(feature.shape)} / {tuple(mask.shape)} / {tuple(labels.shape)}, captured for "
                              f"{tuple(self.feature.shape)} / {tuple(self.mask.shape)} / {tuple(self.labels.shape)}")
@@ -2059,6 +2184,8 @@ class GraphedUnimodalStep:
                 self.mask.copy_(mask, non_blocking=True)
                 self.labels.copy_(labels, non_blocking=True)
         self.graph_a.replay()
+        self.rows = b
+        self.padded_calls += int(b != rows)
         self.i_batch += 1
         if self.i_batch % self.args.trg_accumulation_steps == 0:
             self.graph_b.replay()

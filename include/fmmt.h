@@ -518,6 +518,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_ragged.h"
 /* The metric update that collects a split's logits and labels at a device-held row index (fmmt_eval_accumulate_at): likewise, held to _lib.EVAL_COLLECT_SIGNATURES. */
 #include "fmmt_eval_collect.h"
+/* The pooling head's loss as a mean over the rows that have a label (fmmt_pool_head_fwd_rows / _bwd_rows: a short last batch padded to a captured shape): likewise, held to _lib.POOL_HEAD_ROWS_SIGNATURES. */
+#include "fmmt_pool_head_rows.h"
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,7 @@ extern "C" {
  * fmmt_select_frames_fwd_n: fmmt_select_frames_fwd (fmmt.h; train.py:75-114) on preds [nF = F_cap][NL] whose rows >= *n_valid are padding: the
  *   "did any face of the batch pass the threshold" decision (train.py:80,84) looks at the rows g < *n_valid only -- a padded row above the threshold
  *   must not move the batch from the keep-everything branch to the selection branch.  (Ownership needs no change: an owned face lies below
- *   sum(num_imgs) - (B - 1) <= n_valid.)  n_valid == NULL: fmmt_select_frames_fwd.  The backward is fmmt_select_frames_bwd: a gather through
+ *   the largest utterance boundary max_u (sum_{i<=u} num_imgs_i - u) <= sum(num_imgs) = n_valid.)  n_valid == NULL: fmmt_select_frames_fwd.  The backward is fmmt_select_frames_bwd: a gather through
  *   src_face, which never names a padded row. */
 int fmmt_pack_frames(int B, int Lv, int F_cap, size_t row_bytes, const void* src, const int64_t* num_imgs, void* dst, int32_t* counts, void* stream);
 int fmmt_batchnorm1d_fwd_n(int dtype, int n_cap, int C, const int32_t* n_valid, const void* x, const float* gamma, const float* beta,
