@@ -31,8 +31,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .train_step import (_KEEP_GRAPHS, _ops_pinned_scope, _pin_shadows, capture_window, check_frame_total, distinct_stream, fused_inference,
-                         select_frames)
+from .graph_capture import _KEEP_GRAPHS, capture_window, check_static_shapes, copy_into_static, distinct_stream, require_packet_capture_off, warmup_undone
+from .train_step import _clamp_counts, _pin_shadows, check_frame_total, frame_buckets, fused_inference, pick_bucket, select_frames  # noqa: F401
 
 EMOTIONS = ("Neutral", "Surprise", "Fear", "Sadness", "Joy", "Disgust", "Anger")      # class order of eval_meld (utils/eval_metrics.py:27)
 
@@ -254,31 +254,6 @@ class EvalStep:
         return logits, new_mask
 
 
-def pick_bucket(num_imgs, Lv, buckets):
-    """The capacity a ragged batch is replayed in: the smallest of the ascending `buckets` that holds its sum(clamp(num_imgs, 0, Lv)) real frames
-    when num_imgs is on the host (a list or CPU tensor, as the reference's collate yields it); the LARGEST for a device tensor, which is not
-    read here (that would be a host synchronisation).  A host total above the largest bucket: ValueError, before anything is launched."""
-    if torch.is_tensor(num_imgs):
-        if num_imgs.is_cuda:
-            return buckets[-1]
-        num_imgs = num_imgs.tolist()
-    total = sum(min(max(int(n), 0), int(Lv)) for n in num_imgs)
-    for c in buckets:
-        if total <= c:
-            return c
-    raise ValueError(f"the batch holds {total} face frames, the step was built for frame_capacity={buckets[-1]}")
-
-
-def _clamp_counts(num_imgs, Lv, capacity):
-    """the sample batch's counts cut down, utterance by utterance, until their total fits `capacity`: what a bucket below the sample's total is captured on"""
-    out, room = [], int(capacity)
-    for n in (num_imgs.tolist() if torch.is_tensor(num_imgs) else num_imgs):
-        k = min(max(int(n), 0), int(Lv), room)
-        out.append(k)
-        room -= k
-    return out
-
-
 class GraphedEvalStep:
     """EvalStep's launches captured ONCE as a single HIP graph for the sample batch's shapes -- the text encoder as the one fork branch, the
     layout of GraphedTargetStep's graph A -- and replayed per batch: inputs are copied into static buffers, the metric update is inside the
@@ -300,17 +275,11 @@ class GraphedEvalStep:
 
     def __init__(self, swin_model, multimodal_model, args, batch, autocast_dtype=None, gumbel="sample", metrics=None, overlap_text=True, warmup_iters=2,
                  frame_capacity=None):
-        import os
-        if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0":
-            raise RuntimeError("GraphedEvalStep: DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in the environment before the HIP runtime "
-                               "initialises (see facialmmt_amd/__init__.py)")
+        require_packet_capture_off("GraphedEvalStep")
         self.sample = _check_gumbel(gumbel)
         self.swin, self.mm, self.args, self.autocast_dtype = swin_model, multimodal_model, args, autocast_dtype
-        self.buckets = None
-        if frame_capacity is not None:
-            self.buckets = tuple(int(c) for c in (frame_capacity if isinstance(frame_capacity, (tuple, list)) else (frame_capacity,)))
-            if not self.buckets or self.buckets[0] < 1 or any(a >= b for a, b in zip(self.buckets, self.buckets[1:])):
-                raise ValueError("frame_capacity: a positive number of frames, or an ascending tuple of them")
+        self.buckets = frame_buckets(frame_capacity)
+        if self.buckets is not None:
             _check_padded_frames(batch[8], batch[5])
             check_frame_total(batch[9], batch[8].shape[1], self.buckets[-1])
         self.replays = self.fallbacks = 0
@@ -323,24 +292,19 @@ class GraphedEvalStep:
         self.text_stream = distinct_stream(dev, (cap,)) if overlap_text else None
         collect = getattr(self.metrics, "collect_rows", None)                  # the warm-up passes count into this one, through the same kernel
         scratch = MeldMetrics(self.metrics.num_labels, dev, collect_rows=None if collect is None else len(batch[7]))
-        rng = torch.cuda.get_rng_state(dev)
         self.graphs = {}
         with torch.no_grad(), _eval_mode(self.swin, self.mm), fused_inference():
             for c in self.buckets or (None,):
                 if c is not None:
                     self.static[9].copy_(torch.as_tensor(_clamp_counts(batch[9], batch[8].shape[1], c)))
-                cap.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(cap):
+                with warmup_undone([], dev, cap):                              # an evaluation pass moves nothing but the generator
                     for _ in range(max(1, warmup_iters)):                      # lazy initialisations, the shadow cache the pins are made from
                         scratch.reset()
                         _forward_batch(self.swin, self.mm, args, self.static, scratch, autocast_dtype, self.sample, frame_capacity=c)
-                torch.cuda.current_stream().wait_stream(cap)
-                torch.cuda.synchronize(dev)
-                torch.cuda.set_rng_state(rng, dev)
                 if not self.graphs:
                     self.shadows = _pin_shadows([self.swin, self.mm])
                 graph = torch.cuda.CUDAGraph()
-                with capture_window(), _ops_pinned_scope(self.shadows):
+                with capture_window(), ops.pinned_scope(self.shadows):
                     with torch.cuda.graph(graph, stream=cap):
                         outs = _forward_batch(self.swin, self.mm, args, self.static, self.metrics, autocast_dtype, self.sample, self.text_stream,
                                               self.shadows, frame_capacity=c)
@@ -351,22 +315,20 @@ class GraphedEvalStep:
         self.graph, (self.logits, self.new_mask, self.importance, _) = self.graphs[self.buckets[-1] if self.buckets else None]
 
     def __call__(self, batch):
-        if len(batch) != len(self.static):
-            raise ValueError(f"GraphedEvalStep: batch of {len(batch)} entries, captured with {len(self.static)}")
-        srcs = [s if torch.is_tensor(s) else torch.as_tensor(s) for s in batch]
-        if self.buckets:
-            _check_padded_frames(srcs[8], srcs[5])                             # the compact tensor is an error, not "another shape"
-        if any(tuple(s.shape) != tuple(d.shape) for s, d in zip(srcs, self.static)):
+        try:
+            check_static_shapes(self.static, batch, "GraphedEvalStep")
+        except ValueError:
+            if len(batch) != len(self.static):
+                raise
+            if self.buckets:
+                _check_padded_frames(torch.as_tensor(batch[8]), torch.as_tensor(batch[5]))     # the compact tensor is an error, not "another shape"
             out = self.eager(batch)
             self.fallbacks += 1
             if self.buckets:
                 self.capacity, self.frame_counts, self.importance = self.buckets[-1], self.eager.frame_counts, self.eager.importance
             return out
         c = pick_bucket(batch[9], self.static[8].shape[1], self.buckets) if self.buckets else None
-        with torch.no_grad():
-            for dst, src in zip(self.static, srcs):
-                if dst is not src:
-                    dst.copy_(src, non_blocking=True)
+        copy_into_static(self.static, batch, "GraphedEvalStep")
         self.graph, (self.logits, self.new_mask, self.importance, self.frame_counts) = self.graphs[c]
         self.capacity = c
         self.graph.replay()

@@ -11,6 +11,9 @@ import types
 import torch
 import torch.nn.functional as F
 
+from .graph_capture import (_KEEP_GRAPHS, _bump_versions, _reset_optimizer_state, capture_window, copy_into_static,  # noqa: F401
+                            distinct_stream, pick_concurrent_stream, replay_update, require_packet_capture_off, warmup_undone)
+
 
 SELECT_FRAMES_KERNEL = True      # module constant (tests patch it): False = the torch restatement below (~55 launches)
 
@@ -72,17 +75,40 @@ def select_frames(preds, vision_inputs, vision_mask, num_imgs, threshold, n_vali
     return torch.cat((inputs, emo.to(inputs.dtype)), dim=-1), mask
 
 
-def check_frame_total(num_imgs, Lv, capacity):
-    """Host-side guard of a packed step (frame_capacity): with num_imgs as the reference's collate yields it -- a list or a CPU tensor -- the
-    number of real frames, sum(clamp(n, 0, Lv)), must fit the capacity the step was built for; ValueError otherwise, before anything is launched.
-    A device tensor is not read here (that would be a host synchronisation): the step's `frame_counts` then tells (counts[1] > capacity)."""
+def pick_bucket(num_imgs, Lv, buckets):
+    """The capacity a ragged batch runs in (a training step packs into it, a graphed step replays its capture): the smallest of the ascending
+    `buckets` that holds its sum(clamp(num_imgs, 0, Lv)) real frames when num_imgs is on the host (a list or CPU tensor, as the reference's
+    collate yields it); the LARGEST for a device tensor, which is not read here (that would be a host synchronisation).  A host total above the
+    largest bucket: ValueError, before anything is launched."""
     if torch.is_tensor(num_imgs):
         if num_imgs.is_cuda:
-            return
+            return buckets[-1]
         num_imgs = num_imgs.tolist()
     total = sum(min(max(int(n), 0), int(Lv)) for n in num_imgs)
-    if total > capacity:
-        raise ValueError(f"the batch holds {total} face frames, the step was built for frame_capacity={capacity}")
+    for c in buckets:
+        if total <= c:
+            return c
+    raise ValueError(f"the batch holds {total} face frames, the step was built for frame_capacity={buckets[-1]}")
+
+
+frame_bucket = pick_bucket                                  # the name the training steps call it by: one rule, not a second statement of it
+
+
+def check_frame_total(num_imgs, Lv, capacity):
+    """Host-side guard of a packed step (frame_capacity): pick_bucket with the one capacity the step was built for -- with num_imgs as the
+    reference's collate yields it the real frames must fit it; ValueError otherwise, before anything is launched.  A device tensor is not read:
+    the step's `frame_counts` then tells (counts[1] > capacity)."""
+    pick_bucket(num_imgs, Lv, (capacity,))
+
+
+def _clamp_counts(num_imgs, Lv, capacity):
+    """the sample batch's counts cut down, utterance by utterance, until their total fits `capacity`: what a bucket below the sample's total is captured on"""
+    out, room = [], int(capacity)
+    for n in (num_imgs.tolist() if torch.is_tensor(num_imgs) else num_imgs):
+        k = min(max(int(n), 0), int(Lv), room)
+        out.append(k)
+        room -= k
+    return out
 
 
 def frame_buckets(frame_capacity):
@@ -94,14 +120,6 @@ def frame_buckets(frame_capacity):
     if not caps or caps[0] < 1 or any(a >= b for a, b in zip(caps, caps[1:])):
         raise ValueError(f"frame_capacity: a positive number of frames, or an ascending tuple of them without duplicates, got {frame_capacity!r}")
     return caps
-
-
-def frame_bucket(num_imgs, Lv, capacities):
-    """The capacity a training step runs a ragged batch in: eval_step.pick_bucket's rule, not a second statement of it (the smallest capacity that
-    holds sum(clamp(num_imgs, 0, Lv)) for a list or CPU tensor, ValueError naming the largest when none does; the largest for a device tensor).
-    Imported on the call: eval_step imports this module."""
-    from .eval_step import pick_bucket
-    return pick_bucket(num_imgs, Lv, capacities)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -174,87 +192,6 @@ def pad_aux_batch(images, labels, rows):
     return _pad_const(images, extra), _pad_const(torch.as_tensor(labels), extra, IGNORE_LABEL)
 
 
-def pick_concurrent_stream(device, candidates: int = 8, cycles: int = 4_000_000):
-    """A HIP stream that really runs concurrently with the current one.  HIP multiplexes streams onto a handful of
-    hardware queues (4 by default) and two streams that share a queue serialise; which queue a new stream lands on
-    depends on how many streams the process created before (RCCL, for one, creates several at process-group
-    initialisation -- measured: the text-encoder overlap vanished in every run that had called init_process_group).
-    So measure it: spin kernels on both streams, keep the first candidate whose pair finishes in about the time
-    of one.  Returns (stream, ratio) with ratio = t(pair) / t(single); falls back to the best candidate."""
-    import time
-    main = torch.cuda.current_stream(device)
-
-    def timed(fn):
-        torch.cuda.synchronize(device)
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize(device)
-        return time.perf_counter() - t0
-    torch.cuda._sleep(cycles)                              # warm up the spin kernel
-    single = min(timed(lambda: torch.cuda._sleep(cycles)) for _ in range(3))
-    best, best_ratio, keep = None, float("inf"), []
-    for _ in range(candidates):
-        s = distinct_stream(device, keep)
-        keep.append(s)                                     # keep candidates alive so that the next one is a new stream
-
-        def pair():
-            s.wait_stream(main)
-            torch.cuda._sleep(cycles)
-            with torch.cuda.stream(s):
-                torch.cuda._sleep(cycles)
-        ratio = min(timed(pair) for _ in range(2)) / single
-        if ratio < best_ratio:
-            best, best_ratio = s, ratio
-        if ratio < 1.3:
-            break
-    return best, best_ratio
-
-
-def distinct_stream(device, avoid=()):
-    """A side stream that is a different HIP stream from every stream in `avoid` and from the current one.
-    torch.cuda.Stream() hands out entries of a per-device pool of 32 round-robin: in a process that has created a few dozen
-    streams a "new" stream can BE the capture stream or another branch's stream, and a fork / join between a stream and
-    itself inside a graph capture has crashed the HIP runtime (intermittent segmentation fault in the capture of a step when
-    the whole GPU test suite ran in one process).  So: compare the raw handles and keep drawing."""
-    taken = {s.cuda_stream for s in avoid if s is not None} | {torch.cuda.current_stream(device).cuda_stream}
-    keep = []
-    for _ in range(64):
-        s = torch.cuda.Stream(device=device)
-        if s.cuda_stream not in taken:
-            return s
-        keep.append(s)
-    raise RuntimeError("distinct_stream: the stream pool only returns streams that are already in use")
-
-
-# Captured graphs are never destroyed.  On this ROCm (7.0 runtime under torch 2.10) tearing down HIP graphs that were captured
-# with forked streams is what the intermittent crashes of a long-lived process traced back to: destroyed by a garbage
-# collection during a later capture -> abort inside the capture; destroyed right before the next capture -> segmentation
-# fault in that graph's first replay.  A training process captures a handful of graphs; holding on to them costs nothing.
-_KEEP_GRAPHS = []
-
-
-class capture_window:
-    """Garbage collection fenced off a graph capture: collect NOW (cycles left by earlier steps may own HIP graphs, streams
-    and pool memory whose destructors call into the HIP runtime), then keep the cyclic collector off until the capture ends.
-    torch.cuda.graph stopped collecting on entry (torch >= 2.9 only does with torch.compiler.config.force_cudagraph_gc), and a
-    collection that fires in the middle of a capture destroys such objects while the stream is capturing: measured here as an
-    intermittent abort / segmentation fault of the process (faulthandler: "Garbage-collecting" inside the capture of a step
-    that followed other graph-capturing steps), two runs in five of the whole GPU suite."""
-
-    def __enter__(self):
-        import gc
-        self._was = gc.isenabled()
-        gc.collect()
-        gc.disable()
-        return self
-
-    def __exit__(self, *exc):
-        import gc
-        if self._was:
-            gc.enable()
-        return False
-
-
 class _Branch(torch.nn.Module):
     """One branch of the multimodal forward as a module of its own, so that torch.cuda.make_graphed_callables sees
     exactly the parameters it uses.  Shares the owner's sub-modules (same Parameter objects); never registered on the
@@ -283,11 +220,7 @@ def graph_multimodal(mm, sample_args, autocast_dtype=None, overlap_text=True, pa
     (measured on an MI355X: text encoder 28.4 ms + Swin 52.9 ms = 82.8 ms back to back, 66.9 ms concurrently).
     Returns the module (its forward now replays the graphs)."""
     import contextlib
-    import os
-    if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0":
-        raise RuntimeError("graph_multimodal: DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in the environment before the HIP runtime "
-                           "initialises (import facialmmt_amd before the first CUDA call, or export it): with ROCm 7.0's packet "
-                           "capture, gradients of replayed graphs are wrong from the third replay on")
+    require_packet_capture_off("graph_multimodal")
     ids, attn_mask, sep_mask, audio, audio_mask, vision, vision_mask, utt_idx = sample_args
     utt_idx = torch.as_tensor(utt_idx, device=ids.device)
     plm = mm.roberta if mm.text_pretrained_model == 'roberta' else mm.bert
@@ -845,15 +778,6 @@ def _hand_over_gradients(pairs, flat_view_of, accumulate: bool):
                 torch._foreach_copy_(cast_dst, cast_src)
 
 
-def _restore(snap):
-    """copy the snapshot back, touching only what changed: an untouched buffer keeps its version counter, so host-side
-    caches keyed on it (SwinTransformerBlock._mask_is_standard) stay valid and nothing synchronises inside the capture"""
-    with torch.no_grad():
-        for t, v in snap:
-            if not torch.equal(t, v):
-                t.copy_(v)
-
-
 def step_parameters(mm, masters=None):
     """the parameters the target step's optimizer updates: the multimodal model's, with the text encoder's replaced by
     their fp32 masters when it runs in bf16 (MasterWeights)"""
@@ -861,18 +785,6 @@ def step_parameters(mm, masters=None):
         return [p for p in mm.parameters() if p.requires_grad]
     master_of = {id(l): m for l, m in masters.pairs()}
     return [master_of.get(id(p), p) for p in mm.parameters() if p.requires_grad]
-
-
-def _reset_optimizer_state(opt):
-    """zero every tensor of the optimizer state in place (moments, step counters): undoes the warm-up steps that precede
-    a graph capture without re-allocating the state the captured graph will address"""
-    for st in opt.state.values():
-        for v in st.values():
-            if torch.is_tensor(v):
-                v.zero_()
-    for g in opt.param_groups:                              # HFAdamW keeps its (device) step counter in the group, not in opt.state
-        if torch.is_tensor(g.get("step")):
-            g["step"].zero_()
 
 
 class HFAdamW(torch.optim.Optimizer):
@@ -1130,11 +1042,6 @@ class FusedClipAdamW:
         ops.adamw_batch(self.n, self.blocks, self.desc, self.lr, self.step, self.norm, self.b1, self.b2, self.eps, self.wd, self.max_norm, self.hf)
 
 
-def _ops_pinned_scope(shadows):
-    from . import ops
-    return ops.pinned_scope(shadows)
-
-
 def _pin_shadows(modules):
     """ops.PinnedShadows over the parameters of `modules` (PIN_SHADOWS = False: per-weight casts inside the graph, as before)"""
     if not PIN_SHADOWS:
@@ -1149,17 +1056,62 @@ def _pin_shadows(modules):
     return ops.PinnedShadows(params)
 
 
-def _bump_versions(params):
-    """A graph replay updates parameters in place without autograd noticing: bump their version counters, so that eager code
-    that caches by version (ops._lp: the bf16 weight shadows of an eval() pass after training) rebuilds what it cached."""
-    inc = getattr(torch._C, "_increment_version", None)
-    if inc is None:
-        return
-    try:
-        inc(params)
-    except TypeError:
-        for p in params:
-            inc(p)
+class FlatGradientTail:
+    """What every graphed training step does behind its backward, stated once: the static flat fp32 gradient buffers the optimizer and the
+    all-reduce work on (parallel.GradientAverager's buckets, hooks off: inside a replay no autograd hook fires), the hand-over of the fresh
+    gradients into them, and the update (clip + optimizer step).  The steps differ only in the forward/backward in front of it.
+    `flat`: a GradientAverager(hooks=False), or the parameters to build one over; `masters`: MasterWeights of a sub-module that runs in bf16 --
+    `flat` and the optimizer are then over the fp32 masters (step_parameters); `exchanging`: a gradient exchange runs between hand_over() and
+    update() (the caller's statement, read once: bool(flat.active) where the step exchanges); `capture_tables`: FusedHandOver's `captures`."""
+
+    def __init__(self, flat, opt, clip, accumulate, masters=None, exchanging=False, capture_tables=4):
+        from .parallel import GradientAverager
+        self.opt, self.clip, self.accumulate, self.masters, self.exchanging = opt, clip, bool(accumulate), masters, bool(exchanging)
+        self.flat = flat if isinstance(flat, GradientAverager) else GradientAverager(flat, hooks=False)
+        self.flat_view_of = {p: p.grad for p in self.flat.params}          # the averager made every .grad a view of its bucket
+        low_of = {id(m): l for l, m in (masters.pairs() if masters is not None else [])}
+        self.pairs = [(low_of.get(id(p), p), p) for p in self.flat.params]     # (parameter the model differentiates, parameter the optimizer steps)
+        for l, m in self.pairs:
+            l.grad = None
+        self.fused = None
+        if FusedClipAdamW.eligible(opt, self.flat.params):
+            self.fused = FusedClipAdamW(opt, self.flat.params, self.flat_view_of, low_of, clip)
+        # hand-over and clip norm in one pass; with an exchange between the hand-over and the update (N > 1) the hand-over still runs as one pass, its norm is
+        # discarded and FusedClipAdamW.update takes the norm of the REDUCED buffers in one more launch
+        self.handover = FusedHandOver(len(self.pairs), captures=capture_tables) if (self.fused is not None and FUSED_HANDOVER) else None
+
+    def hand_over(self):
+        """after a backward: the leaves' fresh gradients into the flat buffers (accumulation: added), .grad = None on the leaves -- one pass with the
+        clip norm where FusedHandOver applies, _hand_over_gradients otherwise"""
+        ran = self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm)
+        if not ran:
+            _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
+        # THE RULE for fused.norm_ready: the norm the hand-over left is usable exactly when the fused hand-over ran and no exchange follows it.
+        # With an exchange behind it the norm is of the LOCAL gradients: FusedClipAdamW.update takes it again, of the reduced buffers.
+        if self.fused is not None:
+            self.fused.norm_ready = ran and not self.exchanging
+
+    def update(self):
+        if self.fused is not None:                           # norm + one launch: clip, AdamW, bf16 twins (FusedClipAdamW)
+            self.fused.update()
+        else:
+            for p in self.flat.params:                       # the optimizer reads the static flat buffers
+                p.grad = self.flat_view_of[p]
+            torch.nn.utils.clip_grad_norm_(self.flat.params, self.clip)
+            self.opt.step()
+            if self.masters is not None:
+                self.masters.sync_low()
+        if self.accumulate:
+            self.flat.zero_grad()
+        for l, _ in self.pairs:                              # the next backward must produce fresh gradient tensors
+            l.grad = None
+
+    def undo_warmup(self):
+        """what the warm-up passes in front of a capture left in the optimizer and the flat buffers (graph_capture.warmup_undone calls it)"""
+        _reset_optimizer_state(self.opt)
+        if self.fused is not None:
+            self.fused.reset()
+        self.flat.zero_grad()
 
 
 class GraphedTargetStep:
@@ -1228,7 +1180,7 @@ class GraphedTargetStep:
         cross-row operations are the head's BatchNorm and the filter's "any face passed" (both over the device frame count) and the loss's mean.
         Needs frame_capacity (compact frames change shape with the batch: ValueError) and the default single-graph mode on one rank
         (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
-        import os
+        from . import ops
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
             raise ValueError("discarded_swin_gradients: 'compute' or 'skip'")
@@ -1255,9 +1207,7 @@ class GraphedTargetStep:
                 raise ValueError("frame_capacity: a positive number of frames, and `frames` as the loader pads them, (B, Lv, ...)")
             check_frame_total(batch[9], batch[8].shape[1], self.frame_capacity)
         multi = self.capacities is not None and len(self.capacities) > 1
-        if os.environ.get("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "") != "0":
-            raise RuntimeError("GraphedTargetStep: DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 must be in the environment before the HIP "
-                               "runtime initialises (see facialmmt_amd/__init__.py)")
+        require_packet_capture_off("GraphedTargetStep")
         self.swin, self.mm, self.opt, self.sched, self.args = swin_model, multimodal_model, optimizer, scheduler, args
         self.autocast_dtype = autocast_dtype
         self.i_batch = 0
@@ -1266,24 +1216,13 @@ class GraphedTargetStep:
         # every batch entry becomes a static device tensor: a python list / int baked into the capture would silently be reused
         # by every replay (the reference's collate hands num_imgs and the utterance index over as lists)
         self.static = [t.clone() if torch.is_tensor(t) else torch.as_tensor(t, device=dev) for t in batch]
-        # static flat gradient buffers for the multimodal parameters (hooks off: inside a replay no autograd hook fires)
-        self.masters = masters
-        self.flat = averager if averager is not None else GradientAverager(step_parameters(self.mm, masters), hooks=False)
-        if self.flat._handles:
+        # static flat gradient buffers for the multimodal parameters, hand-over and update: FlatGradientTail
+        flat = averager if averager is not None else GradientAverager(step_parameters(self.mm, masters), hooks=False)
+        if flat._handles:
             raise ValueError("GraphedTargetStep needs GradientAverager(..., hooks=False): the exchange runs between the graphs")
-        self.flat_view_of = {p: p.grad for p in self.flat.params}          # the averager made every .grad a view of its bucket
-        low_of = {id(m): l for l, m in (masters.pairs() if masters is not None else [])}
-        self.pairs = [(low_of.get(id(p), p), p) for p in self.flat.params]     # (parameter the model differentiates, parameter the optimizer steps)
-        for l, m in self.pairs:
-            l.grad = None
-        self.fused = None
-        if FusedClipAdamW.eligible(optimizer, self.flat.params):
-            self.fused = FusedClipAdamW(optimizer, self.flat.params, self.flat_view_of, low_of, args.clip)
-        # hand-over and clip norm in one pass; with an exchange between the hand-over and the update (N > 1) the hand-over still runs as one pass, its norm is
-        # discarded and FusedClipAdamW.update takes the norm of the REDUCED buffers in one more launch
-        self.exchanging = bool(getattr(self.flat, "active", False))
-        self.handover = FusedHandOver(len(self.pairs), captures=max(4, len(self.capacities or ()))) if (self.fused is not None and FUSED_HANDOVER) else None
-        self.accumulate = args.trg_accumulation_steps > 1
+        self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.trg_accumulation_steps > 1, masters=masters, exchanging=bool(flat.active),
+                                            capture_tables=max(4, len(self.capacities or ())))
+        self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         self.mm.text_stream = None
         # inside ONE graph the fork / join below become parallel branches; which hardware queue the branches replay on is the
         # runtime's choice at replay time, not a property of the stream object used during capture
@@ -1301,28 +1240,18 @@ class GraphedTargetStep:
         snap = [(t, t.detach().clone()) for m in (self.swin, self.mm) for t in list(m.parameters()) + list(m.buffers())]
         if masters is not None:
             snap += [(t, t.detach().clone()) for t in masters.masters]
-        rng = torch.cuda.get_rng_state(dev)
         # several capacities: ONE counts word for all captures, and every capacity gets its own warm-up passes (lazy initialisations are per shape) on
-        # the sample's counts cut down to fit it (eval_step._clamp_counts) -- no shape of a pass depends on the counts, only on `_cap`.  After EACH
+        # the sample's counts cut down to fit it (_clamp_counts) -- no shape of a pass depends on the counts, only on `_cap`.  After EACH
         # capacity's passes everything they touched is put back, as the single-capacity constructor does it
         self._counts_buf = torch.empty(2, dtype=torch.int32, device=dev) if multi else None
         for c in self.capacities or (None,):
             if multi:
                 self._use_capacity(c, batch)
-            cap.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(cap):
+            with warmup_undone(snap, dev, cap, tail.undo_warmup):
                 for _ in range(warmup_iters):
                     self._fwd_bwd()
-                    self._update()
+                    tail.update()
                 self.swin.zero_grad(set_to_none=True)
-            torch.cuda.current_stream().wait_stream(cap)
-            torch.cuda.synchronize(dev)
-            _restore(snap)
-            _reset_optimizer_state(self.opt)
-            if self.fused is not None:
-                self.fused.reset()
-            self.flat.zero_grad()
-            torch.cuda.set_rng_state(rng, dev)
         del snap
         # -- capture
         self.shadows = _pin_shadows([self.swin, self.mm])
@@ -1349,7 +1278,7 @@ class GraphedTargetStep:
             # other, and inside a shared pool the capture of the second set would reuse blocks the first set's backward freed
             self.side_stream = distinct_stream(dev, tuple(x for x in (cap, self.text_stream, self.mm.pair_stream) if x is not None))
             self.swin_shadows, self.mm_shadows = _pin_shadows([self.swin]), _pin_shadows([self.mm])
-            with capture_window(), _ops_pinned_scope(self.shadows):
+            with capture_window(), ops.pinned_scope(self.shadows):
                 for k in range(2):
                     frames_k = self.static[8] if k == 0 else self.static[8].clone()
                     g_s, g_a = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -1362,7 +1291,7 @@ class GraphedTargetStep:
                                                            ev_s=torch.cuda.Event(), ev_a=torch.cuda.Event()))
                     _KEEP_GRAPHS.append((g_s, g_a))
                 with torch.cuda.graph(self.graph_b, stream=cap):
-                    self._update()
+                    tail.update()
             self.loss, self.new_mask = self.sets[0].loss, self.sets[0].mask
         elif self.branches:
             # BRANCH_NOTE.  Inside ONE graph the text encoder and Swin are two branches, but the replay does not run them side by side: the
@@ -1379,7 +1308,7 @@ class GraphedTargetStep:
             self.swin_shadows, self.mm_shadows = _pin_shadows([self.swin]), _pin_shadows([self.mm])
             g = types.SimpleNamespace(T=torch.cuda.CUDAGraph(), S=torch.cuda.CUDAGraph(), F=torch.cuda.CUDAGraph(), TB=torch.cuda.CUDAGraph(),
                                       SB=torch.cuda.CUDAGraph(), ev_t=torch.cuda.Event(), ev_f=torch.cuda.Event())
-            with capture_window(), _ops_pinned_scope(self.shadows):
+            with capture_window(), ops.pinned_scope(self.shadows):
                 with torch.cuda.graph(g.T, stream=cap):
                     feat, tmask = self._text_forward()
                 with torch.cuda.graph(g.S, stream=cap):
@@ -1392,11 +1321,11 @@ class GraphedTargetStep:
                     self._bwd_swin((preds, dpreds))
                 del feat, tmask, preds, dfeat, dpreds
                 with torch.cuda.graph(self.graph_b, pool=g.T.pool(), stream=cap):
-                    self._update()
+                    tail.update()
             self.bg = g
             _KEEP_GRAPHS.append((g.T, g.S, g.F, g.TB, g.SB))
         else:
-          with capture_window(), _ops_pinned_scope(self.shadows):
+          with capture_window(), ops.pinned_scope(self.shadows):
             if self.split:
                 with torch.cuda.graph(self.graph_a, stream=cap):
                     self.loss, self.new_mask, swin_out = self._fwd_bwd_multimodal()
@@ -1424,7 +1353,7 @@ class GraphedTargetStep:
                     self.swin.zero_grad(set_to_none=True)
                 self.loss, self.new_mask = loss, new_mask
                 with torch.cuda.graph(self.graph_b, stream=cap):
-                    self._update()
+                    tail.update()
             else:
                 before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
                 with torch.cuda.graph(self.graph_a, stream=cap):
@@ -1434,7 +1363,7 @@ class GraphedTargetStep:
                     self.capture_reserved_bytes[self.frame_capacity] = torch.cuda.memory_reserved(dev) - before[1]
             if not multi:
                 with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
-                    self._update()
+                    tail.update()
         _KEEP_GRAPHS.append((self.graph_a, self.graph_a2, self.graph_b))
         if multi:
             self._use_capacity(self.capacities[-1], batch)  # the sample's own counts (they fit the largest capacity) back in the static input
@@ -1490,7 +1419,7 @@ class GraphedTargetStep:
             self._bwd_swin((preds, dpreds))
         cap.wait_stream(ts)
         cap.wait_stream(ss)
-        self._hand_over()
+        self.tail.hand_over()
         return loss, new_mask
 
     def _text_forward(self, refresh=True):
@@ -1531,27 +1460,12 @@ class GraphedTargetStep:
                 if gr is not None:
                     l.grad = gr if l.grad is None else l.grad + gr      # (a parameter both pieces use: none in this model)
         if handover:
-            self._hand_over()
-
-    def _hand_over(self):
-        if self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm):
-            self.fused.norm_ready = True
-        else:
-            _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
-            if self.fused is not None:
-                self.fused.norm_ready = False
+            self.tail.hand_over()
 
     def _call_branches(self, batch):
         g, main, side = self.bg, torch.cuda.current_stream(), self.side_stream
         main.wait_stream(side)                              # the previous step's side-stream work read the static inputs
-        with torch.no_grad():
-            for i, (dst, src) in enumerate(zip(self.static, batch)):
-                if dst is src:
-                    continue
-                src = src if torch.is_tensor(src) else torch.as_tensor(src)
-                if tuple(src.shape) != tuple(dst.shape):
-                    raise ValueError(f"GraphedTargetStep: batch entry {i} has shape {tuple(src.shape)}, the captured graphs are for {tuple(dst.shape)}")
-                dst.copy_(src, non_blocking=True)
+        copy_into_static(self.static, batch, "GraphedTargetStep")
         side.wait_stream(main)
         with torch.cuda.stream(side):
             g.T.replay()
@@ -1585,7 +1499,6 @@ class GraphedTargetStep:
 
     def _use_capacity(self, c, batch):
         """several capacities: the next warm-up / capture packs into `c`, on the sample batch's counts cut down to fit it"""
-        from .eval_step import _clamp_counts
         self._cap = c
         with torch.no_grad():
             self.static[9].copy_(torch.as_tensor(_clamp_counts(batch[9], batch[8].shape[1], c)))
@@ -1673,10 +1586,7 @@ class GraphedTargetStep:
         loss = F.cross_entropy(logits.float(), labels) / args.trg_accumulation_steps
         if whole:                                            # one piece: autograd runs the text branch's backward beside Swin's
             loss.backward()
-            if self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm):
-                self.fused.norm_ready = not self.exchanging     # with an exchange behind it the norm is taken again, of the reduced buffers (FusedClipAdamW.update)
-            else:
-                _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
+            self.tail.hand_over()
             return loss.detach(), new_mask, None
         # backward, first piece: every leaf the optimizer steps plus Swin's output (the autograd graph below `preds` -- Swin -- is
         # left untouched, with its saved activations, for the second piece)
@@ -1706,10 +1616,7 @@ class GraphedTargetStep:
         # (Letting the fused update read the model's own .grad tensors instead -- no hand-over, 2.8 GB less traffic -- was
         #  tried: the ~870 gradient tensors then stay allocated across the graph and the step got 2.8 ms SLOWER; not kept.)
         # N > 1 (two-piece backward): the same one-pass hand-over in front of the exchange; its norm is of the LOCAL gradients and is discarded
-        if not (self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm)):
-            _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
-        if self.fused is not None:
-            self.fused.norm_ready = False
+        self.tail.hand_over()
         return loss.detach(), new_mask, (x_cut, dpreds)
 
     # two-piece backward: cut behind Swin stage SWIN_CUT.  Measured at one rank with the exchange forced (ms per step, same call; the
@@ -1723,21 +1630,6 @@ class GraphedTargetStep:
         preds, dpreds = swin_out
         if dpreds is not None:
             torch.autograd.backward(preds, dpreds)
-
-    def _update(self):
-        if self.fused is not None:                           # norm + one launch: clip, AdamW, bf16 twins (FusedClipAdamW)
-            self.fused.update()
-        else:
-            for p in self.flat.params:                       # the optimizer reads the static flat buffers
-                p.grad = self.flat_view_of[p]
-            torch.nn.utils.clip_grad_norm_(self.flat.params, self.args.clip)
-            self.opt.step()
-            if self.masters is not None:
-                self.masters.sync_low()
-        if self.accumulate:
-            self.flat.zero_grad()
-        for l, _ in self.pairs:                              # the next backward must produce fresh gradient tensors
-            l.grad = None
 
     def _swin_version(self):
         ps = self._swin_params
@@ -1760,14 +1652,7 @@ class GraphedTargetStep:
 
     def _call_pipelined(self, batch, next_batch):
         k, st = self.cur, self.sets[self.cur]
-        with torch.no_grad():
-            for i, (dst, src) in enumerate(zip(self.static, batch)):
-                if i == 8 or dst is src:
-                    continue
-                src = src if torch.is_tensor(src) else torch.as_tensor(src)
-                if tuple(src.shape) != tuple(dst.shape):
-                    raise ValueError(f"GraphedTargetStep: batch entry {i} has shape {tuple(src.shape)}, the captured graphs are for {tuple(dst.shape)}")
-                dst.copy_(src, non_blocking=True)
+        copy_into_static(self.static, batch, "GraphedTargetStep", skip=(8,))      # the frames belong to graph S (_launch_swin)
         pf = self.prefetched
         if not (pf is not None and pf[0] == k and pf[1] is batch[8] and pf[2] == batch[8]._version and pf[3] == self._swin_version()):
             self._launch_swin(k, batch[8])                  # nothing (valid) prefetched: Swin's forward for this batch, in order
@@ -1780,12 +1665,7 @@ class GraphedTargetStep:
         st.A.replay()
         st.ev_a.record(main)
         self.cur = k ^ 1
-        self.i_batch += 1
-        if self.i_batch % self.args.trg_accumulation_steps == 0:
-            self.graph_b.replay()
-            _bump_versions(self.flat.params)
-            if self.sched is not None:
-                self.sched.step()
+        replay_update(self, self.args.trg_accumulation_steps)
         self.loss, self.new_mask = st.loss, st.mask
         return st.loss, st.mask
 
@@ -1811,14 +1691,7 @@ class GraphedTargetStep:
             c = frame_bucket(batch[9], self.static[8].shape[1], self.capacities)
             if self._graphs:
                 graph_a = self._graphs[c][0]
-        with torch.no_grad():
-            for i, (dst, src) in enumerate(zip(self.static, batch)):
-                if dst is src:
-                    continue
-                src = src if torch.is_tensor(src) else torch.as_tensor(src)
-                if tuple(src.shape) != tuple(dst.shape):
-                    raise ValueError(f"GraphedTargetStep: batch entry {i} has shape {tuple(src.shape)}, the captured graphs are for {tuple(dst.shape)}")
-                dst.copy_(src, non_blocking=True)
+        copy_into_static(self.static, batch, "GraphedTargetStep")
         graph_a.replay()
         self.rows = b
         self.padded_calls += int(b != rows)
@@ -1925,101 +1798,59 @@ class GraphedAuxStep:
         pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
         device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
         (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
+        from . import ops
         from .parallel import GradientAverager
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
-        self.images, self.labels = images.clone(), labels.clone()
+        self.static = [images.clone(), labels.clone()]
         self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
         self.n_valid = torch.full((1,), images.shape[0], dtype=torch.int32, device=images.device) if self.pad_rows else None
         self.shadows = None
         self.i_batch = 0
         dev = images.device
-        self.flat = averager if averager is not None else GradientAverager(self.swin.parameters(), hooks=False)
-        self.flat_view_of = {p: p.grad for p in self.flat.params}
-        self.pairs = [(p, p) for p in self.flat.params]
-        self.fused = FusedClipAdamW(optimizer, self.flat.params, self.flat_view_of, {}, args.clip) if FusedClipAdamW.eligible(optimizer, self.flat.params) else None
-        self.exchanging = bool(getattr(self.flat, "active", False))
-        self.handover = FusedHandOver(len(self.flat.params)) if (self.fused is not None and FUSED_HANDOVER) else None
-        for p in self.flat.params:
-            p.grad = None
-        self.accumulate = args.aux_accumulation_steps > 1
+        flat = averager if averager is not None else GradientAverager(self.swin.parameters(), hooks=False)
+        self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.aux_accumulation_steps > 1, exchanging=bool(flat.active))
+        self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.swin.parameters()) + list(self.swin.buffers())]
-        rng = torch.cuda.get_rng_state(dev)
         cap = distinct_stream(dev)
-        cap.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cap):
+        with warmup_undone(snap, dev, cap, tail.undo_warmup):
             for _ in range(warmup_iters):
                 self._fwd_bwd()
-                self._update()
-        torch.cuda.current_stream().wait_stream(cap)
-        torch.cuda.synchronize(dev)
-        _restore(snap)
+                tail.update()
         del snap
-        _reset_optimizer_state(self.opt)
-        if self.fused is not None:
-            self.fused.reset()
-        self.flat.zero_grad()
-        torch.cuda.set_rng_state(rng, dev)
         self.shadows = _pin_shadows([self.swin])
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with capture_window(), _ops_pinned_scope(self.shadows):
+        with capture_window(), ops.pinned_scope(self.shadows):
             with torch.cuda.graph(self.graph_a, stream=cap):
                 self.loss = self._fwd_bwd()
             with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
-                self._update()
+                tail.update()
         _KEEP_GRAPHS.append((self.graph_a, self.graph_b))
         self.flat.zero_grad()
 
     def _fwd_bwd(self):
         if self.shadows is not None:
             self.shadows.refresh()
+        images, labels = self.static
         if self.pad_rows:
-            loss = self.swin(self.images, False, self.labels, F.cross_entropy, n_valid=self.n_valid) / self.args.aux_accumulation_steps
+            loss = self.swin(images, False, labels, F.cross_entropy, n_valid=self.n_valid) / self.args.aux_accumulation_steps
         else:
-            loss = self.swin(self.images, False, self.labels, F.cross_entropy) / self.args.aux_accumulation_steps
+            loss = self.swin(images, False, labels, F.cross_entropy) / self.args.aux_accumulation_steps
         loss.backward()
-        if self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm):
-            self.fused.norm_ready = not self.exchanging      # N > 1: the norm is taken again over the reduced buffers
-        else:
-            _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
+        self.tail.hand_over()
         return loss.detach()
 
-    def _update(self):
-        if self.fused is not None:
-            self.fused.update()
-        else:
-            for p in self.flat.params:
-                p.grad = self.flat_view_of[p]
-            torch.nn.utils.clip_grad_norm_(self.flat.params, self.args.clip)
-            self.opt.step()
-        if self.accumulate:
-            self.flat.zero_grad()
-        for p in self.flat.params:                           # the next backward must produce fresh gradient tensors
-            p.grad = None
-
     def __call__(self, images, labels):
-        rows = b = self.images.shape[0]
-        if self.pad_rows and images.dim() == self.images.dim() and images.shape[0] != rows:
+        rows = b = self.static[0].shape[0]
+        if self.pad_rows and images.dim() == self.static[0].dim() and images.shape[0] != rows:
             b = images.shape[0]
             images, labels = pad_aux_batch(images, labels, rows)     # ValueError for b == 0 or b > rows, before any copy or launch
-        if tuple(images.shape) != tuple(self.images.shape) or tuple(labels.shape) != tuple(self.labels.shape):
-            raise ValueError(f"GraphedAuxStep: batch of shape {tuple(images.shape)} / {tuple(labels.shape)}, captured for "
-                             f"{tuple(self.images.shape)} / {tuple(self.labels.shape)}")
-        with torch.no_grad():
-            if images is not self.images:
-                self.images.copy_(images, non_blocking=True)
-                self.labels.copy_(labels, non_blocking=True)
-            if self.n_valid is not None:
-                self.n_valid.fill_(b)                        # a device fill: no host synchronisation
+        copy_into_static(self.static, (images, labels), "GraphedAuxStep")
+        if self.n_valid is not None:
+            self.n_valid.fill_(b)                            # a device fill: no host synchronisation
         self.graph_a.replay()
         self.rows = b
         self.padded_calls += int(b != rows)
-        self.i_batch += 1
-        if self.i_batch % self.args.aux_accumulation_steps == 0:
-            self.flat.exchange_all()                         # Swin's gradients: 187 MB fp32, nothing left in the step to hide them behind
-            self.graph_b.replay()
-            _bump_versions(self.flat.params)
-            if self.sched is not None:
-                self.sched.step()
+        replay_update(self, self.args.aux_accumulation_steps, self.flat.exchange_all)     # Swin's gradients: 187 MB fp32, nothing left in the step to hide them behind
         return self.loss
 
     def start_epoch(self):
@@ -2094,47 +1925,32 @@ class GraphedUnimodalStep:
     trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
 
     def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False):
-        from .parallel import GradientAverager
+        from . import ops
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
         self.autocast_dtype = autocast_dtype
         feature, mask, labels = batch
-        self.feature, self.mask, self.labels = feature.clone(), mask.clone(), torch.as_tensor(labels, device=feature.device).clone()
+        self.static = [feature.clone(), mask.clone(), torch.as_tensor(labels, device=feature.device).clone()]
         self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
         self.shadows = None
         self.i_batch = 0
         dev = feature.device
-        self.flat = GradientAverager(self.model.parameters(), hooks=False)
-        self.flat_view_of = {p: p.grad for p in self.flat.params}
-        self.pairs = [(p, p) for p in self.flat.params]
-        self.fused = FusedClipAdamW(optimizer, self.flat.params, self.flat_view_of, {}, args.clip) if FusedClipAdamW.eligible(optimizer, self.flat.params) else None
-        self.handover = FusedHandOver(len(self.flat.params)) if (self.fused is not None and FUSED_HANDOVER) else None
-        for p in self.flat.params:
-            p.grad = None
-        self.accumulate = args.trg_accumulation_steps > 1
+        # this step never exchanges (exchanging=False): the hand-over's norm is always the update's
+        self.tail = tail = FlatGradientTail(self.model.parameters(), optimizer, args.clip, args.trg_accumulation_steps > 1)
+        self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.model.parameters()) + list(self.model.buffers())]
-        rng = torch.cuda.get_rng_state(dev)
         cap = distinct_stream(dev)
-        cap.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cap):
+        with warmup_undone(snap, dev, cap, tail.undo_warmup):
             for _ in range(warmup_iters):
                 self._fwd_bwd()
-                self._update()
-        torch.cuda.current_stream().wait_stream(cap)
-        torch.cuda.synchronize(dev)
-        _restore(snap)
+                tail.update()
         del snap
-        _reset_optimizer_state(self.opt)
-        if self.fused is not None:
-            self.fused.reset()
-        self.flat.zero_grad()
-        torch.cuda.set_rng_state(rng, dev)
         self.shadows = _pin_shadows([self.model])
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with capture_window(), _ops_pinned_scope(self.shadows):
+        with capture_window(), ops.pinned_scope(self.shadows):
             with torch.cuda.graph(self.graph_a, stream=cap):
                 self.loss = self._fwd_bwd()
             with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
-                self._update()
+                tail.update()
         _KEEP_GRAPHS.append((self.graph_a, self.graph_b))
         self.flat.zero_grad()
 
@@ -2142,56 +1958,29 @@ class GraphedUnimodalStep:
         if self.shadows is not None:
             self.shadows.refresh()
         kw = {"valid_mean": True} if self.pad_rows else {}
+        feature, mask, labels = self.static
         if self.autocast_dtype is not None:
             with torch.autocast("cuda", dtype=self.autocast_dtype, cache_enabled=False):
-                loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels, **kw)
+                loss, logits = self.model.forward_loss(feature, mask, labels, **kw)
         else:
-            loss, logits = self.model.forward_loss(self.feature, self.mask, self.labels, **kw)
+            loss, logits = self.model.forward_loss(feature, mask, labels, **kw)
         self.logits = logits.detach()
         loss = loss / self.args.trg_accumulation_steps
         loss.backward()
-        if self.handover is not None and self.handover(self.pairs, self.flat_view_of, self.accumulate, self.fused.norm):
-            self.fused.norm_ready = True
-        else:
-            _hand_over_gradients(self.pairs, self.flat_view_of, self.accumulate)
+        self.tail.hand_over()
         return loss.detach()
-
-    def _update(self):
-        if self.fused is not None:
-            self.fused.update()
-        else:
-            for p in self.flat.params:
-                p.grad = self.flat_view_of[p]
-            torch.nn.utils.clip_grad_norm_(self.flat.params, self.args.clip)
-            self.opt.step()
-        if self.accumulate:
-            self.flat.zero_grad()
-        for p in self.flat.params:                           # the next backward must produce fresh gradient tensors
-            p.grad = None
 
     def __call__(self, batch):
         feature, mask, labels = batch
-        rows = b = self.feature.shape[0]
-        if self.pad_rows and feature.dim() == self.feature.dim() and feature.shape[0] != rows:
+        rows = b = self.static[0].shape[0]
+        if self.pad_rows and feature.dim() == self.static[0].dim() and feature.shape[0] != rows:
             b = feature.shape[0]
             feature, mask, labels = pad_unimodal_batch(batch, rows)     # ValueError for b == 0 or b > rows, before any copy or launch
-        if tuple(feature.shape) != tuple(self.feature.shape) or tuple(mask.shape) != tuple(self.mask.shape) or tuple(labels.shape) != tuple(self.labels.shape):
-            raise ValueError(f"GraphedUnimodalStep: batch of shape {tuple(feature.shape)} / {tuple(mask.shape)} / {tuple(labels.shape)}, captured for "
-                             f"{tuple(self.feature.shape)} / {tuple(self.mask.shape)} / {tuple(self.labels.shape)}")
-        with torch.no_grad():
-            if feature is not self.feature:
-                self.feature.copy_(feature, non_blocking=True)
-                self.mask.copy_(mask, non_blocking=True)
-                self.labels.copy_(labels, non_blocking=True)
+        copy_into_static(self.static, (feature, mask, labels), "GraphedUnimodalStep")
         self.graph_a.replay()
         self.rows = b
         self.padded_calls += int(b != rows)
-        self.i_batch += 1
-        if self.i_batch % self.args.trg_accumulation_steps == 0:
-            self.graph_b.replay()
-            _bump_versions(self.flat.params)
-            if self.sched is not None:
-                self.sched.step()
+        replay_update(self, self.args.trg_accumulation_steps)
         return self.loss
 
     def start_epoch(self):

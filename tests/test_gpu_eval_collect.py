@@ -150,7 +150,7 @@ def test_the_cursor_moves_inside_a_captured_graph(dev):
     """ONE captured MeldMetrics.update, replayed five times on changing inputs: the rows land at 0, B, 2B, ... -- the launch arguments are frozen,
     the cursor is not -- and a second run gives the same bits"""
     from facialmmt_amd.eval_step import MeldMetrics
-    from facialmmt_amd.train_step import _KEEP_GRAPHS, capture_window
+    from facialmmt_amd.graph_capture import _KEEP_GRAPHS, capture_window
     nl, B, reps = 7, 33, 5
     m = MeldMetrics(nl, dev, collect_rows=reps * B)
     s_logits, s_labels = torch.zeros(B, nl, device=dev), torch.zeros(B, dtype=torch.int64, device=dev)

@@ -77,7 +77,7 @@ def test_scheduled_step_equals_eager_step(mode):
         assert (p0[k] - p1[k]).abs().max().item() <= 1e-4 * max(1.0, p0[k].abs().max().item()), k
 
 
-def _run_six(dev, graphed, accumulation, bf16_plm=False, adamw=False, swin_gradients="compute", pipeline=False):
+def _run_six(dev, graphed, accumulation, bf16_plm=False, adamw=False, swin_gradients="compute", pipeline=False, mode=None):
     from facialmmt_amd import models
     from facialmmt_amd.config import default_args
     from facialmmt_amd.train_step import GraphedTargetStep, TargetStep
@@ -113,7 +113,8 @@ def _run_six(dev, graphed, accumulation, bf16_plm=False, adamw=False, swin_gradi
     else:
         opt = torch.optim.SGD(mm.parameters(), lr=0.05)
     if graphed:
-        step = GraphedTargetStep(swin, mm, opt, None, cfg, batch, autocast_dtype=None, masters=masters, discarded_swin_gradients=swin_gradients, pipeline_swin=pipeline)
+        step = GraphedTargetStep(swin, mm, opt, None, cfg, batch, autocast_dtype=None, masters=masters, discarded_swin_gradients=swin_gradients, pipeline_swin=pipeline,
+                                 **({mode: True} if mode else {}))
         assert step.text_stream is not None
         assert (step.fused is not None) == adamw
     else:
@@ -159,6 +160,23 @@ def test_pipelined_swin_forward_walks_the_in_order_trajectory(accumulation):
     dev = torch.device("cuda:0")
     l0, p0, rm0, nb0, k0 = _run_six(dev, False, accumulation)
     l1, p1, rm1, nb1, k1 = _run_six(dev, True, accumulation, pipeline=True)
+    assert l0[0] != l0[-1]
+    for a, b in zip(l0, l1):
+        assert abs(a - b) <= 2e-4 * max(1.0, abs(a)), (l0, l1)
+    for k in p0:
+        assert (p0[k] - p1[k]).abs().max().item() <= 1e-4 * max(1.0, p0[k].abs().max().item()), k
+    assert nb0 == nb1 and torch.allclose(rm0, rm1, rtol=1e-5, atol=1e-6)
+    assert torch.equal(k0, k1)
+
+
+@pytest.mark.parametrize("mode", ["branch_graphs", "fork_streams"])
+def test_not_adopted_capture_modes_walk_the_in_order_trajectory(mode):
+    """GraphedTargetStep(branch_graphs=True) (every branch a graph of its own, BRANCH_NOTE) and (fork_streams=True) (one graph forked behind a tick,
+    FORK_NOTE): measured and not adopted, but both run the shared hand-over and update -- same comparisons and tolerances as the pipelined test above
+    against the in-order eager step, six steps, noise-free configuration, one micro-step per update."""
+    dev = torch.device("cuda:0")
+    l0, p0, rm0, nb0, k0 = _run_six(dev, False, 1)
+    l1, p1, rm1, nb1, k1 = _run_six(dev, True, 1, mode=mode)
     assert l0[0] != l0[-1]
     for a, b in zip(l0, l1):
         assert abs(a - b) <= 2e-4 * max(1.0, abs(a)), (l0, l1)
