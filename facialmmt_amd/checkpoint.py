@@ -18,7 +18,10 @@ What the reference does and what replaces it:
 The reference's loop tests `k in pretrained_dict` with the *model's* key before reading
 `pretrained_dict['backbone.' + name]` (train.py:320-329), which only matches files that hold both spellings;
 here a tensor is taken whenever `backbone.<name>` is present, and what was and was not found is returned so the
-caller can see it rather than silently training from random weights."""
+caller can see it rather than silently training from random weights.
+
+* Nothing in the reference continues a stopped run.  -> `save_training`, `load_training`: one file of the training steps' states
+  (`state_dict()` of train_step's step classes, step_state.py) plus builtins such as the epoch."""
 from __future__ import annotations
 
 import collections
@@ -144,3 +147,46 @@ def load_state(model, source, strict: bool = True) -> LoadReport:
             loaded.append(k)
     model.load_state_dict(new, strict=True)
     return LoadReport(loaded, missing, unused, mismatched)
+
+
+TRAINING_FORMAT = 1
+
+
+def _require_plain(obj, where):
+    """tensors on the CPU and builtins only, all the way down: what torch.load(weights_only=True) reads back"""
+    if type(obj) is torch.Tensor:
+        if obj.device.type != "cpu":
+            raise TypeError(f"{where} is a tensor on {obj.device}: a training file holds CPU tensors (a step's state_dict() yields them)")
+    elif type(obj) in (dict, collections.OrderedDict):
+        for k, v in obj.items():
+            if not isinstance(k, (str, int)):
+                raise TypeError(f"{where}: key {k!r} is {type(k).__name__}, not a str or an int")
+            _require_plain(v, f"{where}[{k!r}]")
+    elif type(obj) in (list, tuple):
+        for i, v in enumerate(obj):
+            _require_plain(v, f"{where}[{i}]")
+    elif not (obj is None or type(obj) in (bool, int, float, str)):
+        raise TypeError(f"{where} is {type(obj).__name__}: a training file holds tensors and builtins only")
+
+
+def save_training(path: str, extra: Dict[str, object] | None = None, **states) -> None:
+    """Write the named states of a run's training steps and `extra` into one file, e.g.
+    `save_training(path, extra={"epoch": 3, "best_f1": 0.66}, aux=step_a.state_dict(), target=step_t.state_dict())`.  CPU tensors and builtins
+    only (TypeError otherwise, nothing written), so `load_training` reads it with weights_only=True; written beside `path` and moved over it, so
+    the last good file is never half-written.
+    The auxiliary and the target step both hold Swin (and share the device's generator): both states carry its weights, identical at save time,
+    so loading them in either order leaves Swin as it was saved."""
+    payload = {"format": TRAINING_FORMAT, "states": dict(states), "extra": dict(extra or {})}
+    _require_plain(payload, "save_training")
+    tmp = f"{path}.tmp.{os.getpid()}"
+    torch.save(payload, tmp)
+    os.replace(tmp, path)
+
+
+def load_training(path: str):
+    """Read a file written by `save_training` (weights_only=True: tensors and builtins) -> (states, extra): `states[name]` goes to
+    `load_state_dict` of a constructed step of the same kind, in any order (see save_training); ValueError for another format."""
+    payload = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(payload, dict) or payload.get("format") != TRAINING_FORMAT or set(payload) != {"format", "states", "extra"}:
+        raise ValueError(f"{path}: not a training file of format {TRAINING_FORMAT}")
+    return payload["states"], payload["extra"]

@@ -13,6 +13,8 @@ import torch.nn.functional as F
 
 from .graph_capture import (_KEEP_GRAPHS, _bump_versions, _reset_optimizer_state, capture_window, copy_into_static,  # noqa: F401
                             distinct_stream, pick_concurrent_stream, replay_update, require_packet_capture_off, warmup_undone)
+from . import step_state
+from .step_state import StepState
 
 
 SELECT_FRAMES_KERNEL = True      # module constant (tests patch it): False = the torch restatement below (~55 launches)
@@ -270,11 +272,12 @@ def graph_multimodal(mm, sample_args, autocast_dtype=None, overlap_text=True, pa
 SKIP_NOTE = "Swin's target-step gradients are never read (train.py:20,33,140-143): 'skip' does not compute them"
 
 
-class TargetStep:
+class TargetStep(StepState):
     """Swin (train mode, Gumbel-softmax head) -> frame filter -> multimodal model -> CE -> backward ->
     (every `accumulation_steps`) clip + AdamW + schedule, as train.py:46-143.  Only the multimodal
     optimizer steps here; Swin receives gradients through the emotion features and is updated by the
     auxiliary task's optimizer (train.py:31), so its gradients are dropped after each step."""
+    STATE_KIND, STATE_MODELS, STATE_WINDOW = "target", ("swin", "mm"), "trg_accumulation_steps"
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, autocast_dtype=None, ddp_model=None, averager=None,
                  discarded_swin_gradients="compute", frame_capacity=None):
@@ -732,16 +735,18 @@ class MasterWeights:
     def sync_low(self):
         torch._foreach_copy_(self.low, self.masters)
 
+    def fp32_items(self):
+        """[(key of the module's state_dict, the LIVE fp32 tensor that holds its value)]: the master of every stepped parameter, the kept fp32
+        copy of everything else that was rounded -- the one statement of which keys a checkpoint takes from where (state_dict_fp32, step_state)"""
+        keys = set(self.module.state_dict().keys())
+        by_id = {id(p): m for p, m in zip(self.low, self.masters)}
+        out = [(k, by_id[id(p)]) for k, p in self.module.named_parameters() if id(p) in by_id and k in keys]
+        return out + [(k, t) for k, t in self.frozen_fp32.items() if k in keys]
+
     def state_dict_fp32(self):
         """the module's state_dict with the master values in place of the rounded ones (what a checkpoint should hold)"""
         sd = {k: v.detach().clone() for k, v in self.module.state_dict().items()}
-        by_id = {id(p): m for p, m in zip(self.low, self.masters)}
-        for k, p in self.module.named_parameters():
-            if id(p) in by_id:
-                sd[k] = by_id[id(p)].detach().clone()
-        for k, t in self.frozen_fp32.items():
-            if k in sd:
-                sd[k] = t.clone()
+        sd.update({k: t.detach().clone() for k, t in self.fp32_items()})
         return sd
 
 
@@ -1008,9 +1013,11 @@ class FusedClipAdamW:
     def load_from(self, opt):
         """take moments and step counter from `opt` (after HFAdamW.load_hf_state_dict / Optimizer.load_state_dict of a checkpoint): this object
         keeps its own m, v and step -- the ones the captured update addresses -- so a loaded optimizer state must be copied IN, in place.
-        Parameters the optimizer holds no state for keep zero moments."""
+        Parameters the optimizer holds no state for keep zero moments.  The loaded group's betas / eps / weight decay must be this object's:
+        the captured update holds them as launch arguments, so others cannot take effect -- ValueError, nothing copied."""
         params = self.keep[0]
         g = opt.param_groups[0]
+        step_state.check_hyper(g, {"betas": (self.b1, self.b2), "eps": self.eps, "weight_decay": self.wd}, "FusedClipAdamW.load_from")
         for p, m, v in zip(params, self.m, self.v):
             st = opt.state.get(p, {})
             if "exp_avg" in st:
@@ -1026,6 +1033,14 @@ class FusedClipAdamW:
                 raise ValueError(f"per-parameter step counters disagree: {sorted(ts)}")
             t = ts.pop() if ts else 0.0
         self.step.fill_(float(t))
+
+    @torch.no_grad()
+    def export(self, params=None):
+        """the inverse of load_from: (first moments, second moments, update count) on the HOST, one tensor per parameter of `params` (default:
+        this object's own order), copied tensor by tensor -- no second device copy of the moments; nothing of this object or the optimizer changes"""
+        at = {id(p): i for i, p in enumerate(self.keep[0])}
+        order = [at[id(p)] for p in (self.keep[0] if params is None else params)]
+        return [step_state.to_host(self.m[i]) for i in order], [step_state.to_host(self.v[i]) for i in order], int(self.step.item())
 
     @torch.no_grad()
     def update(self):
@@ -1113,8 +1128,40 @@ class FlatGradientTail:
             self.fused.reset()
         self.flat.zero_grad()
 
+    # -- the graphed half of a step's state_dict() / load_state_dict() (step_state.py; the eager half: step_state.EagerTail)
+    def require_single_rank(self, what):
+        if self.flat.active:
+            raise NotImplementedError(f"{what}: one rank only (not with an active gradient exchange: per-rank generator state is not saved)")
 
-class GraphedTargetStep:
+    def optimizer_state(self):
+        """the optimizer's state in its class's own layout, on the host: from FusedClipAdamW where the fused update keeps it (`optimizer.state` stays
+        empty), from the optimizer otherwise"""
+        if self.fused is None:
+            return step_state.stock_optimizer_state(self.opt)
+        return step_state.optimizer_state(self.opt, *self.fused.export(step_state.optimizer_params(self.opt)))
+
+    def window(self):
+        """the gradients of an open accumulation window: the flat views, in the optimizer's order, as fp32 host tensors"""
+        return [step_state.to_host(self.flat_view_of[p]) for p in step_state.optimizer_params(self.opt)]
+
+    def check_window(self, who):
+        if any(p not in self.flat_view_of for p in step_state.optimizer_params(self.opt)):
+            raise RuntimeError(f"{who}: the optimizer steps a parameter the flat gradient buffers do not hold")
+
+    @torch.no_grad()
+    def load(self, optimizer, window):
+        """a checked optimizer state and window (None: no window is open) into the tensors the captured graphs address, in place"""
+        step_state.load_optimizer_state(optimizer, self.opt, self.fused)
+        if window is None:
+            self.flat.zero_grad()
+        else:
+            for p, src in zip(step_state.optimizer_params(self.opt), window):
+                self.flat_view_of[p].copy_(src)
+        for l, _ in self.pairs:
+            l.grad = None
+
+
+class GraphedTargetStep(StepState):
     """The whole target-task step as HIP graphs, replayed per step with one host call each -- two graphs (A = A1 + A2 as one, then B) on
     a single GPU, three when a gradient exchange has to be hidden (N > 1):
 
@@ -1135,6 +1182,8 @@ class GraphedTargetStep:
     shadows re-cast inside the graph.  Shapes are static: __call__ copies the batch into the captured input buffers.
     `accumulation_steps` > 1 replays A that many times per B (gradients accumulate in the flat buffers).
     Parity: tests/test_gpu_train_step.py walks this against the eager TargetStep (same losses, same parameters)."""
+
+    STATE_KIND, STATE_MODELS, STATE_WINDOW = TargetStep.STATE_KIND, TargetStep.STATE_MODELS, TargetStep.STATE_WINDOW
 
     # where the text branch's launches enter the capture order: "start" (in front of Swin's forward), "pe" (behind PatchEmbed), "s<i>"
     # (behind Swin stage i).  A class constant the probes patch (PATCH="train_step.GraphedTargetStep.TEXT_FORK_AT='s0'" tools/probes/bench_patch.py),
@@ -1789,9 +1838,10 @@ def pick_swin_cut(exchange_ms_alone: float, frames: int = 640, tail_ms: dict | N
     return 2
 
 
-class GraphedAuxStep:
+class GraphedAuxStep(StepState):
     """The auxiliary-task step (train.py:15-41: Swin -> logits -> cross-entropy -> backward -> clip -> AdamW on the Swin
     model) as two HIP graphs, same construction as GraphedTargetStep; the Swin gradients are the exchanged ones here."""
+    STATE_KIND, STATE_MODELS, STATE_WINDOW = "aux", ("swin",), "aux_accumulation_steps"
 
     def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False):
         """`pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
@@ -1859,10 +1909,11 @@ class GraphedAuxStep:
         self.flat.zero_grad()
 
 
-class AuxStep:
+class AuxStep(StepState):
     """One auxiliary-task (Aff-Wild2 frame classification) step, train.py:15-41: Swin -> logits (no Gumbel)
     -> cross-entropy -> backward -> clip (0.8) -> AdamW on the Swin model (aux_lr 5e-5) every
     `aux_accumulation_steps`.  BASELINE.json configs[4] alternates these steps with target steps per epoch."""
+    STATE_KIND, STATE_MODELS, STATE_WINDOW = GraphedAuxStep.STATE_KIND, GraphedAuxStep.STATE_MODELS, GraphedAuxStep.STATE_WINDOW
 
     def __init__(self, swin_model, optimizer, scheduler, args):
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
@@ -1881,11 +1932,12 @@ class AuxStep:
         return loss.detach()
 
 
-class UnimodalStep:
+class UnimodalStep(StepState):
     """One V-only training step, train.py:245-273 (choice_modality 'V'): meld_utt_transformer on pre-extracted face features -> cross-entropy /
     trg_accumulation_steps -> backward; every trg_accumulation_steps micro-steps clip over the model's parameters (args.clip), optimizer step,
     scheduler step, gradients cleared.  batch = (modality_feature, utterance_mask, labels); returns the detached micro-loss.  The tail behind the
     encoder -- pooling, dropout, classifier, loss -- is models.meld_utt_transformer.forward_loss (ops.pool_head_loss)."""
+    STATE_KIND, STATE_MODELS, STATE_WINDOW = "unimodal", ("model",), "trg_accumulation_steps"
 
     def __init__(self, model, optimizer, scheduler, args):
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
@@ -1911,7 +1963,7 @@ class UnimodalStep:
         self.opt.zero_grad(set_to_none=True)
 
 
-class GraphedUnimodalStep:
+class GraphedUnimodalStep(StepState):
     """UnimodalStep as two HIP graphs, the construction of GraphedAuxStep: graph A = bf16 shadow refresh, forward_loss, backward, gradient hand-over into
     flat fp32 buffers (+ the clip norm); graph B = clip + optimizer step (one fused launch for AdamW / HFAdamW with a device learning rate).  The warm-up
     passes run on a side stream and are undone (parameter snapshot, optimizer state zeroed); the dropout seeds are drawn on the device inside graph A,
@@ -1923,6 +1975,7 @@ class GraphedUnimodalStep:
     same bits as the plain loss on a full batch --, and a batch with 1 <= b <= B rows is padded to B by pad_unimodal_batch (copies of row 0, label
     -100) and replayed through the same graphs, flat buffers and optimizer state; the loss returned is the mean over the b real rows /
     trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
+    STATE_KIND, STATE_MODELS, STATE_WINDOW = UnimodalStep.STATE_KIND, UnimodalStep.STATE_MODELS, UnimodalStep.STATE_WINDOW
 
     def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False):
         from . import ops
