@@ -313,8 +313,7 @@ int wa_groups_per_head(int B_, int nH, bool bwd, bool mfma) {
     //   MFMA fwd: 36 KB LDS, 116 VGPR -> 4 per CU (1024);  MFMA bwd (two waves per window): 57 KB LDS, <= 256
     //   registers -> 2 per CU (512);
     //   fp32 VALU kernels: ~8 / 1-2 per CU, parity path only.
-    static const int fwd_wgs = fmmt_const("FMMT_WA_FWD_WGS", 1024);
-    const int target = mfma ? (bwd ? 512 : fwd_wgs) : 2048;
+    const int target = mfma ? (bwd ? 512 : 1024) : 2048;
     int g = target / nH;
     const int wpi = (mfma && bwd) ? 2 : 4;      // windows per workgroup iteration (MFMA backward: two waves per window)
     const int maxg = (B_ + wpi - 1) / wpi;
@@ -326,8 +325,7 @@ int wa_groups_per_head(int B_, int nH, bool bwd, bool mfma) {
 }
 
 int wa_xcd_grouped(int groups_per_head, bool mfma) {
-    static const int on = fmmt_const("FMMT_WA_XCD", 1);
-    return (on && mfma && groups_per_head % 8 == 0) ? 1 : 0;
+    return (mfma && groups_per_head % 8 == 0) ? 1 : 0;
 }
 
 int wa_check(int dtype, int n_img, int H, int W, int C, int nH, int shift) {

@@ -24,11 +24,6 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 #define FMMT_DT_F32 0
 #define FMMT_DT_BF16 1
 
-// Dispatch constants.  Each of these was an environment switch while its A/B was open (rounds 1-2: tile shapes, ring depths, epilogue
-// routes, thresholds ...); the measured winner is compiled in and the name stays as the label DESIGN.md refers to.  The library
-// reads NO environment variable.
-constexpr int fmmt_const(const char*, int winner) { return winner; }
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute: one flag word per call site, one bit per device (a process
 // that drives several GPUs -- a C-ABI consumer without torch's one-process-per-GPU habit -- sets it on each), atomically (launchers may be
 // called from autograd's worker threads).  Returns 0 or the hipError.

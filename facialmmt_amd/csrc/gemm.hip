@@ -358,9 +358,9 @@ __global__ __launch_bounds__(512) void linear_nt_deep_kernel(LinArgs p) {
         cur = cur == 2 ? 0 : cur + 1;
     }
     // epilogue through LDS, as in linear_nt_deep32_kernel: plain / bias through the block-wide slab, everything else through
-    // wave-private slabs (FMMT_NT_SLAB=0 / FMMT_NT_WSLAB=0: straight from the accumulator layout)
+    // wave-private slabs
     const bool plain = p.epi == 0 && !p.y_pre && !p.res && !p.aux && !p.rowscale;
-    if (p.part || (p.reserved & (plain ? 16 : 32))) {
+    if (p.part) {
         nt_epilogue<T, MT, NT>(p, acc, m0 + wm * 64, n0 + wn * 64, li, lg);
     } else if (plain) {
         nt_epilogue_slab<T, MT, NT, 2, BN, 512>(p, acc, smem, wm, wn, li, lg, tid, m0, n0);
@@ -477,9 +477,9 @@ void linear_nt_deep32_kernel(LinArgs p) {
             cur = cur == 2 ? 0 : cur + 1;
         }
     }
-    // FMMT_NT_SLAB=0 (p.reserved bit 4): the older epilogue, straight from the accumulator layout (A/B switch)
+    // split-K partials and the 96-wide tile's operand / GELU epilogues: straight from the accumulator layout
     const bool plain = p.epi == 0 && !p.y_pre && !p.res && !p.aux && !p.rowscale;
-    if (p.part || (p.reserved & 16) || (!plain && (BN != 128 || (p.reserved & 32)))) {
+    if (p.part || (!plain && BN != 128)) {
         nt_epilogue<T, MT, NT>(p, acc, m0 + wm * 64, n0 + wn * WN, li, lg);
     } else if (plain) {
         nt_epilogue_slab<T, MT, NT, 2, BN, 512>(p, acc, smem, wm, wn, li, lg, tid, m0, n0);
@@ -557,16 +557,18 @@ __device__ __forceinline__ void nt_read_frags(bf16x8 (&o)[NF], const unsigned (&
     }
 }
 
+// BK and BATCH have one value each (they stay in the parameter list: profiles and bench.py key on the kernel names).  K step 64 with a ring
+// of 2 (3 for the 128-wide tile) won on every shape by 3-17 % over K step 32 with a ring of 4 (half the barriers,
+// profiles/r02_gemm_shapes.txt); BATCH: the fragment reads of a K block as one inline-asm statement (nt_read_frags).
 template <int BN, int BK, int NBUF, bool BATCH = true, bool HASOP = false, bool PIPE = false>
 __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
-
+    static_assert(BK == 64 && BATCH, "one K step, batched fragment reads");
     using T = bf16;
     constexpr int BM = 256, PITCH = BK, MT = 8, NT = BN / 64, WN = BN / 4, CW = 4 * NT;
-    constexpr int RPI = BK == 64 ? 8 : 16;                 // tile rows per DMA instruction (64 lanes x 16 B = 1 KB)
+    constexpr int RPI = 8;                                 // tile rows per DMA instruction (64 lanes x 16 B = 1 KB)
     constexpr int STAGE = (BN + BM) * PITCH;               // elements per ring stage: BN weight rows, then 256 token rows
     constexpr int NI = (BN + BM) / RPI;                    // DMA instructions per stage, dealt round-robin to the 8 waves
     constexpr int CNT_LO = NI / 8;
-    static_assert(BK == 32 || BK == 64, "K step");
     static_assert(BN % 64 == 0 && (NBUF - 2) * (CNT_LO + 2) <= 63, "tile / vmcnt immediate");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     T* S = reinterpret_cast<T*>(smem);                                              // [NBUF][BN + 256][BK]
@@ -582,14 +584,14 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
 
     typedef __attribute__((address_space(1))) const void gptr_t;
     typedef __attribute__((address_space(3))) void lptr_t;
-    auto key = [](int row) { return BK == 64 ? ((row >> 1) & 7) : (((row >> 3) ^ (row >> 2)) & 3); };   // 16-byte chunk swizzle
-    const int rl = BK == 64 ? (lane >> 3) : (lane >> 2), cl = BK == 64 ? (lane & 7) : (lane & 3);
-    // Weight rows sit in LDS in FRAGMENT order (K step 64): row wn * WN + b * 16 + i of the stage holds the output channel that
+    auto key = [](int row) { return (row >> 1) & 7; };     // 16-byte chunk swizzle
+    const int rl = lane >> 3, cl = lane & 7;
+    // Weight rows sit in LDS in FRAGMENT order: row wn * WN + b * 16 + i of the stage holds the output channel that
     // lane i of n-tile b accumulates (chan_of), so that a weight fragment read touches 16 consecutive 128-byte rows like a token
     // fragment does -- with the rows in channel order the lanes of one ds_read_b128 phase met rows {0-3, 24-27} and {8-11, 16-19},
     // whose swizzle keys coincide pairwise: 2-way bank conflicts on every 8-channel-chunk fragment (SQ_LDS_BANK_CONFLICT 19 % of
-    // the LDS cycles).  FMMT_NT_P256_WROWS=0 (reserved bit 64): channel order (A/B switch).
-    const bool wperm = BK == 64 && !(p.reserved & 64);
+    // the LDS cycles).  (HASOP keeps the choice a run-time value that is always true: see LinArgs::chan_rows.)
+    const bool wperm = HASOP ? !p.chan_rows : true;
     auto wchan = [&](int r) {
         const int w = r / WN, q = r - w * WN;
         return wperm ? w * WN + chan_of<CW>(q >> 4, (q >> 2) & 3, q & 3) : r;
@@ -667,38 +669,21 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
     }
     const unsigned lds0 = (unsigned)(uintptr_t)(lptr_t*)S;
     auto compute = [&](int slot) {
-        if constexpr (BATCH) {
-            const unsigned sbase = lds0 + (unsigned)slot * (unsigned)(STAGE * 2);
-#pragma unroll
-            for (int kk = 0; kk < BK / 32; ++kk) {
-                // second half of a 64-wide K step: chunk index + 4 -> the swizzled chunk offset flips bit 2 (32 elements = 64 bytes)
-                unsigned ad[NT + MT];
-#pragma unroll
-                for (int b = 0; b < NT; ++b) ad[b] = (((unsigned)woff[b] * 2u) ^ (kk ? 64u : 0u)) + sbase;
-#pragma unroll
-                for (int a = 0; a < MT; ++a) ad[NT + a] = (((unsigned)xoff[a] * 2u) ^ (kk ? 64u : 0u)) + sbase;
-                bf16x8 fr[NT + MT];
-                nt_read_frags<NT + MT>(fr, ad);
-#pragma unroll
-                for (int a = 0; a < MT; ++a)
-#pragma unroll
-                    for (int b = 0; b < NT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[b], fr[NT + a], acc[a][b], 0, 0, 0);
-            }
-        } else {
-        const T* sb = S + slot * STAGE;
+        const unsigned sbase = lds0 + (unsigned)slot * (unsigned)(STAGE * 2);
 #pragma unroll
         for (int kk = 0; kk < BK / 32; ++kk) {
-            // second half of a 64-wide K step: chunk index + 4 -> the swizzled chunk offset flips bit 2 (32 elements)
-            bf16x8 wf[NT], xf[MT];
+            // second half of a 64-wide K step: chunk index + 4 -> the swizzled chunk offset flips bit 2 (32 elements = 64 bytes)
+            unsigned ad[NT + MT];
 #pragma unroll
-            for (int b = 0; b < NT; ++b) wf[b] = *reinterpret_cast<const bf16x8*>(sb + (kk ? (woff[b] ^ 32) : woff[b]));
+            for (int b = 0; b < NT; ++b) ad[b] = (((unsigned)woff[b] * 2u) ^ (kk ? 64u : 0u)) + sbase;
 #pragma unroll
-            for (int a = 0; a < MT; ++a) xf[a] = *reinterpret_cast<const bf16x8*>(sb + (kk ? (xoff[a] ^ 32) : xoff[a]));
+            for (int a = 0; a < MT; ++a) ad[NT + a] = (((unsigned)xoff[a] * 2u) ^ (kk ? 64u : 0u)) + sbase;
+            bf16x8 fr[NT + MT];
+            nt_read_frags<NT + MT>(fr, ad);
 #pragma unroll
             for (int a = 0; a < MT; ++a)
 #pragma unroll
-                for (int b = 0; b < NT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[b], xf[a], acc[a][b], 0, 0, 0);
-        }
+                for (int b = 0; b < NT; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fr[b], fr[NT + a], acc[a][b], 0, 0, 0);
         }
     };
 
@@ -754,8 +739,8 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
     char* scratch = smem + (size_t)NBUF * STAGE * sizeof(T) + 2 * 256 * sizeof(float) + (size_t)wm * PR * SP;
     // (K > 1536: the tile's 48+ K steps dwarf the epilogue and the passes' sixteen barriers cost more than the stores save:
     //  31360 x 768 x 3072 measured 153 us direct, 165 us through LDS)
-    const bool lds_gelu = p.epi == FMMT_EPI_GELU && !(p.reserved & 8);      // GELU (+ pre-activation): two tensors through the slab
-    const bool lds_epi = !HASOP && (p.epi == 0 || lds_gelu) && (!p.y_pre || lds_gelu) && !p.part && !(p.reserved & 4) && p.K <= 1536;
+    // (GELU + pre-activation through these block-wide slabs as well -- two tensors, 16-row passes, 32 barriers per tile -- measured slower: 273 -> 296 us)
+    const bool lds_epi = !HASOP && p.epi == 0 && !p.y_pre && !p.part && p.K <= 1536;
     T* __restrict__ yg = reinterpret_cast<T*>(p.y);
     // PIPE: fragment reads software-pipelined against the MFMAs.  The eight waves of the workgroup pass the K step's barrier
     // together, so with "read a K block's fragments, wait, issue its MFMAs" they all queue on the LDS at once (88 KB per K block
@@ -818,7 +803,7 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
     // same phase.  Moving groups of pieces under later micro-batches trades issue-phase cycles for DMA-wait cycles (a stage has
     // one K step to land): worth 5-10 % at K >= 768, nothing at K = 384, a loss at K = 192; turns taken by wave class within a
     // micro-batch (SIMD partners in different classes): 0-5 % slower.
-    constexpr int NG = BN == 256 ? 1 : 2;                  // same-call A/B of 1 / 2 / 3 groups, see launch_p256
+    constexpr int NG = BN == 256 ? 1 : 2;                  // (1 / 2 / 3 groups measured in the same call)
     auto issue_group = [&](int g) {
         if (!pend) return;
         const unsigned kbyte = (unsigned)ik * (BK * 2);
@@ -830,8 +815,7 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
             issue_advance();
         }
     };
-    if constexpr (PIPE) {
-        static_assert(BK == 64 && BATCH, "pipelined reads: 64-deep K steps (the weight buffers alternate by K block)");
+    if constexpr (PIPE) {                                  // (needs the 64-deep K step: the weight buffers alternate by K block)
         if (nsteps > 0) {
             sync_stage(0, 0, first);
             issue_group(0);
@@ -883,11 +867,10 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
                     for (int a = 0; a < MT; ++a) acc[a][b] += bb;
                 }
             }
-            // (GELU + pre-activation through the block-wide slabs of the narrower tiles: FMMT_NT_P256_LDSGELU=1; measured 281 -> 292 us, off.)
             // Round 6: the GELU launches (+ pre-activation or derivative: TWO output tensors) of the 256-wide tile take the wave-private slabs as well --
-            // straight from the accumulator layout they were 16-row x 64-byte partial-line stores, twice (FMMT_NT_P256_WAVEGELU=0: as before).
+            // straight from the accumulator layout they were 16-row x 64-byte partial-line stores, twice.
             const bool gelu_any = p.epi == FMMT_EPI_GELU || p.epi == FMMT_EPI_GELU_DG;
-            if (BN == 256 && !HASOP && !p.part && !(p.reserved & 4) && ((p.epi == 0 && !p.y_pre) || (gelu_any && !(p.reserved & 128)))) {
+            if (BN == 256 && !HASOP && !p.part && ((p.epi == 0 && !p.y_pre) || gelu_any)) {
                 // 256-wide tile: a wave's 64 channels are one 128-byte line, so the transposition is wave-private -- 16 token rows
                 // at a time through this wave's own 2.3 KB slab, no barrier -- and serves GELU + pre-activation (two tensors) too
                 if constexpr (BN == 256) {
@@ -961,9 +944,8 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
                 }
             } else if (lds_epi) {
                 const int rows_left = p.M - (m0 + wm * 128);             // token rows of this wave group that exist
-                T* __restrict__ ypre = reinterpret_cast<T*>(p.y_pre);
-                // one slab round: the waves park `which` (0: the values as they are, 1: their GELU) of PR rows, then store whole rows
-                auto round = [&](int pass, T* dst, bool gelu) {
+                // one slab round: the waves park PR rows, then store whole rows
+                auto round = [&](int pass) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();                          // the slab's previous rows have been read
 #pragma unroll
@@ -972,23 +954,15 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
                         char* row = scratch + (f * 16 + li) * SP + (wn * WN) * 2;
 #pragma unroll
                         for (int c = 0; c < NT / 2; ++c) {
-                            float t[8];
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) t[e] = acc[a][2 * c + (e >> 2)][e & 3];
-                            if (gelu) gelu_inplace<T>(t, 8);
                             bf16x8 v;
 #pragma unroll
-                            for (int e = 0; e < 8; ++e) v[e] = (bf16)t[e];
+                            for (int e = 0; e < 8; ++e) v[e] = (bf16)acc[a][2 * c + (e >> 2)][e & 3];
                             *reinterpret_cast<bf16x8*>(row + chan_of<CW>(2 * c, lg, 0) * 2) = v;
                         }
                         if constexpr (NT % 2) {
-                            float t[4];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) t[e] = acc[a][NT - 1][e];
-                            if (gelu) gelu_inplace<T>(t, 4);
                             bf16x4 v;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = (bf16)t[e];
+                            for (int e = 0; e < 4; ++e) v[e] = (bf16)acc[a][NT - 1][e];
                             *reinterpret_cast<bf16x4*>(row + chan_of<CW>(NT - 1, lg, 0) * 2) = v;
                         }
                     }
@@ -1000,18 +974,14 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
                         const int row = pass * PR + r;
                         if (row < rows_left) {
                             const bf16x8 v = *reinterpret_cast<const bf16x8*>(scratch + r * SP + cc * 16);
-                            __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(dst + (size_t)(m0 + wm * 128 + row) * p.ldy + n0 + cc * 8));
+                            __builtin_nontemporal_store(v, reinterpret_cast<bf16x8*>(yg + (size_t)(m0 + wm * 128 + row) * p.ldy + n0 + cc * 8));
                         }
                     }
                 };
-                const bool two = lds_gelu && ypre != nullptr;
 #pragma unroll
-                for (int pass = 0; pass < 128 / PR; ++pass) {
-                    if (two) round(pass, ypre, false);
-                    round(pass, yg, lds_gelu);
-                }
+                for (int pass = 0; pass < 128 / PR; ++pass) round(pass);
                 // a wave group with all its 128 rows inside M issued exactly this many stores per wave (ragged panel: unknown -> 0)
-                if (!PIPE && rows_left >= 128) st_prev = (128 / PR) * NSL * (two ? 2 : 1);
+                if (!PIPE && rows_left >= 128) st_prev = (128 / PR) * NSL;
             } else if constexpr (HASOP) {
                 nt_epilogue<T, MT, NT, true, true>(p, acc, m0 + wm * 128, n0 + wn * WN, li, lg, &pre);
             } else {
@@ -1037,68 +1007,48 @@ int launch_p256_b(const LinArgs& a, hipStream_t st) {
     LinArgs p = a;
     p.tiles_m = (a.M + 255) / 256;
     p.tiles_n = a.N / BN;
-    // FMMT_NT_P256_LDSEPI=0: epilogue stores straight from the accumulator layout (A/B switch)
-    static const int lds_epi = fmmt_const("FMMT_NT_P256_LDSEPI", 1);
-    static const int lds_gelu = fmmt_const("FMMT_NT_P256_LDSGELU", 0);   // measured slower (two tensors, 16-row passes: 32 barriers per tile): 273 -> 296 us
-    static const int wrows = fmmt_const("FMMT_NT_P256_WROWS", 1);
-    static const int wave_gelu = fmmt_const("FMMT_NT_P256_WAVEGELU", 1);   // round 6: the two-tensor GELU epilogues of the 256-wide tile through the wave-private slabs
-    p.reserved = (lds_epi ? 0 : 4) | (lds_gelu ? 0 : 8) | (wrows ? 0 : 64) | (wave_gelu ? 0 : 128);
     hipLaunchKernelGGL((linear_nt_p256_kernel<BN, BK, NBUF, BATCH, HASOP, PIPE>), dim3(256), dim3(512), lds, st, p);
     FMMT_CHECK_LAUNCH();
     return 0;
 }
 template <int BN, int BK, int NBUF>
 int launch_p256(const LinArgs& a, hipStream_t st) {
-    // FMMT_NT_P256_BATCH=0: fragment reads left to the compiler's schedule (A/B switch)
-    static const int batch = fmmt_const("FMMT_NT_P256_BATCH", 1);
     if constexpr (BN != 256) {
         // launches with an M x N epilogue operand or a DropPath scale: operand prefetched into registers (48 / 32 of them:
-        // no room beside the 128 accumulators of the 256-wide tile)
+        // no room beside the 128 accumulators of the 256-wide tile).  (Operand-free launches that store directly, K > 1536, were tried
+        // on this instantiation as well: against the pipelined loop below it loses, 135 -> 127 us, same call.)
         if (a.res || a.aux || a.rowscale) return launch_p256_b<BN, BK, NBUF, true, true>(a, st);
-        // FMMT_NT_P256_PLAINOP: 1 = operand-free launches whose epilogue stores directly (K > 1536) take the operand-prefetch
-        // instantiation as well (round 2: 31360 x 768 x 3072 160 -> 153 us); against the pipelined loop below it loses (135 -> 127 us,
-        // same call): 0
-        static const int plainop = fmmt_const("FMMT_NT_P256_PLAINOP", 0);
-        if (plainop && !a.part && (a.K > 1536 || plainop > 1)) return launch_p256_b<BN, BK, NBUF, true, true>(a, st);
     }
-    if constexpr (BK == 64) {
-        // Pipelined fragment reads + DMA pieces in groups (PIPE), for K >= 384.  Same-call A/B against the plain loop, us per
-        // launch: 31360 x 2304 x 768 124 -> 115, 31360 x 3072 x 768 150 -> 141, 31360 x 768 x 768 44.4 -> 41.2, 125440 x 1536 x 384
-        // (256-wide tile, one group) 190 -> 178, 125440 x 384 x 384 52.7 -> 50.2, 125440 x 1152 x 384 / 384 x 1536 / 384 x 1152 +-1 %;
-        // K = 192 (three K steps per tile: the late pieces are waited for) 210 -> 220, stays on the plain loop.
-        static const int pipe = fmmt_const("FMMT_NT_P256_PIPE", 1);
-        if (pipe && a.K >= 384) return launch_p256_b<BN, BK, NBUF, true, false, true>(a, st);
-    }
-    return batch ? launch_p256_b<BN, BK, NBUF, true, false>(a, st) : launch_p256_b<BN, BK, NBUF, false, false>(a, st);
+    // Pipelined fragment reads + DMA pieces in groups (PIPE), for K >= 384.  Same-call A/B against the plain loop, us per
+    // launch: 31360 x 2304 x 768 124 -> 115, 31360 x 3072 x 768 150 -> 141, 31360 x 768 x 768 44.4 -> 41.2, 125440 x 1536 x 384
+    // (256-wide tile, one group) 190 -> 178, 125440 x 384 x 384 52.7 -> 50.2, 125440 x 1152 x 384 / 384 x 1536 / 384 x 1152 +-1 %;
+    // K = 192 (three K steps per tile: the late pieces are waited for) 210 -> 220, stays on the plain loop.
+    if (a.K >= 384) return launch_p256_b<BN, BK, NBUF, true, false, true>(a, st);
+    return launch_p256_b<BN, BK, NBUF, true, false>(a, st);
 }
 
 // Tile choice for the persistent kernel: the widest channel tile that divides N, unless a narrower one fills the last
 // round of 256 workgroups better (31360 tokens x 768 channels: 369 tiles of 256 x 256 = 2 rounds at 72 %, 492 tiles of
 // 256 x 192 = 2 rounds at 96 %).  Returns 0 if the shape is not for this kernel.
 int p256_plan(const LinArgs& a) {
-    static const int mode = fmmt_const("FMMT_NT_P256", 1);       // 0: off; 256 / 192 / 128: force that tile
-    // K % 64 != 0 (Swin stage 0: K = 96, three K steps of 32): only with FMMT_NT_P256_K32=1 (A/B switch)
-    static const int k32 = fmmt_const("FMMT_NT_P256_K32", 0);
-    static const int minm = fmmt_const("FMMT_NT_P256_MINM", 16384);      // fewest tokens for this kernel
-    if (!mode || a.ksplit || a.M < minm || a.M % 16 || a.K % 32 || a.K < 96 || a.ldx % 8 || a.ldw % 8) return 0;
-    if (a.K % 64 && !k32) return 0;
+    constexpr int P256_MINM = 16384;                       // fewest tokens for this kernel
+    // (K % 64 != 0 -- Swin stage 0: K = 96 -- stays on the deep / single-step kernels)
+    if (a.ksplit || a.M < P256_MINM || a.M % 16 || a.K % 64 || a.K < 96 || a.ldx % 8 || a.ldw % 8) return 0;
     if ((unsigned long long)a.M * a.ldx >= (1ull << 31) || (unsigned long long)a.N * a.ldw >= (1ull << 31)) return 0;   // 32-bit byte offsets of the DMA pieces
     // One workgroup per CU has nothing to hide an epilogue's own M x N loads behind (residual, GELU' operand, DropPath
     // scale: the in-order vmcnt also makes them wait for the DMA stages in flight).  Measured on MI355X
     // (profiles/r02_gemm_shapes.txt): plain / bias / GELU + pre-activation launches gain 5-50 % over the two-workgroup
-    // 256 x 128 kernels (125440 x 1536 x 384 GELU: 0.439 -> 0.295 ms), launches with such loads lose 0-25 %: those stay
-    // on the older kernels.  FMMT_NT_P256=2 sends them here as well (A/B switch).
-    // FMMT_NT_P256_OPS: 1 (default) = launches with a residual and / or DropPath scale come here too, on the 192- / 128-wide
-    // tiles, with the operand prefetched into registers one K step before the epilogue (HASOP): measured, same call, 321 -> 262 us
-    // (501760 x 192 x 768), 210 -> 201 (125440 x 384 x 1536); 2 = GELU' launches as well: 338 -> 391 / 530 -> 614 us -- that
-    // epilogue is ~11 k VALU cycles per wave tile against 4.6 k MFMA cycles of a K = 384 tile, and one workgroup per CU has no
-    // second workgroup whose K loop could run under it; 0 = none.
-    // (round 4: mode 2 re-measured with gelu' from an LDS table in this kernel's unused epilogue scratch instead of the polynomial: 125440 x 1536 x 384
-    //  328 -> 364 us, 501760 x 768 x 192 522 -> 561, 31360 x 3072 x 768 267 -> 253 -- still a loss where it matters; stays 1.
+    // 256 x 128 kernels (125440 x 1536 x 384 GELU: 0.439 -> 0.295 ms).
+    // Launches with a residual and / or DropPath scale come here too, on the 192- / 128-wide tiles, with the operand prefetched
+    // into registers one K step before the epilogue (HASOP): measured, same call, 321 -> 262 us (501760 x 192 x 768), 210 -> 201
+    // (125440 x 384 x 1536).  GELU' launches (an aux operand) do not: 338 -> 391 / 530 -> 614 us -- that epilogue is ~11 k VALU
+    // cycles per wave tile against 4.6 k MFMA cycles of a K = 384 tile, and one workgroup per CU has no second workgroup whose K
+    // loop could run under it.
+    // (round 4: re-measured with gelu' from an LDS table in this kernel's unused epilogue scratch instead of the polynomial: 125440 x 1536 x 384
+    //  328 -> 364 us, 501760 x 768 x 192 522 -> 561, 31360 x 3072 x 768 267 -> 253 -- still a loss where it matters.
     //  And once more with the polynomial GELU' that replaced the tables: 314 -> 340, 491 -> 529, 258 -> 241 us.)
-    static const int ops_mode = fmmt_const("FMMT_NT_P256_OPS", 1);
     const bool has_op = a.res || a.aux || a.rowscale;
-    if (has_op && (!ops_mode || (a.aux && (ops_mode < 2 || a.res)) || a.ldres % 8 || a.ldaux % 8)) return 0;
+    if (has_op && (a.aux || a.ldres % 8 || a.ldaux % 8)) return 0;
     const int tm = (a.M + 255) / 256;
     int best = 0;
     double best_cost = 0;
@@ -1108,7 +1058,6 @@ int p256_plan(const LinArgs& a) {
         const int bn = cand[i];
         if (a.N % bn) continue;
         if (has_op && bn == 256) continue;
-        if (mode > 2 && mode != bn) continue;
         const int tiles = tm * (a.N / bn);
         if (tiles < 256) continue;
         const double cost = (double)((tiles + 255) / 256) * bn * pen[i];
@@ -1149,15 +1098,14 @@ int dispatch_nt_bk(const LinArgs& a, hipStream_t st) {
         if (!a.ksplit && a.K <= 64) return launch_nt<T, BM, BN, 64, 1>(a, st);     // PatchEmbed (K = 48)
         // measured on MI355X (tools/probes/gemm_bench.py, sum over the bench shapes): BK=64 5.33 ms vs BK=32 5.88 ms
         // direct global->LDS DMA staging: measured +7 % over register staging summed over the bench shapes, up to
-        // +25 % on the K >= 768 ones (971 TF/s on 31360x768x3072); FMMT_NT_GLDS=0 selects the register-staged kernel
-        static const int glds = fmmt_const("FMMT_NT_GLDS", 1);
-        if (glds && a.K % 64 == 0 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
+        // +25 % on the K >= 768 ones (971 TF/s on 31360x768x3072)
+        if (a.K % 64 == 0 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
             // four-buffer ring for few-token problems with a long K loop and at most one workgroup per CU (fc2 of the
             // encoder FFNs, 512-1328 tokens x 768 x 3072: 32 -> 25 us); with more tiles than CUs the 96 KB ring costs
-            // co-residency (1328 x 3072 x 768: 15 -> 21 us), and at K = 768 it is a wash.  FMMT_NT_GLDS=2: never.
+            // co-residency (1328 x 3072 x 768: 15 -> 21 us), and at K = 768 it is a wash.
             if constexpr (BM == 64) {
                 const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-                if (glds != 2 && a.K >= 2048 && tiles <= 256) return launch_nt<T, BM, BN, 64, 4, true>(a, st);
+                if (a.K >= 2048 && tiles <= 256) return launch_nt<T, BM, BN, 64, 4, true>(a, st);
             }
             return launch_nt<T, BM, BN, 64, 2, true>(a, st);
         }
@@ -1180,9 +1128,8 @@ int dispatch_nt_bk(const LinArgs& a, hipStream_t st) {
 //                    behind the MFMAs of a phase, on the workgroup's critical path, and a short K loop has few phases to amortise it);
 //   GELU'            loses everywhere (262 -> 828): stays on the persistent kernel.
 int ph_plan(const LinArgs& a, int* epi3) {
-    static const int on = fmmt_const("FMMT_NT_PH", 1);
     const bool mul_aux = a.epi == FMMT_EPI_MUL_AUX && a.aux && !a.res && !a.y_pre && !a.bias;
-    if (!on || a.ksplit || a.part || (a.aux && !mul_aux)) return 0;
+    if (a.ksplit || a.part || (a.aux && !mul_aux)) return 0;
     const bool gelu_pre = a.epi == FMMT_EPI_GELU && a.y_pre, has_op = a.res || a.rowscale;
     if (!gelu_pre && !mul_aux && (a.epi != 0 || a.y_pre)) return 0;
     if (gelu_pre && (has_op || a.K < 1536)) return 0;
@@ -1223,9 +1170,8 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
     // few-token problems (cross-modal encoder: 152..1280 rows; embedding head: 640 rows) use 64-row tiles so
     // that twice as many workgroups share the work; the multi-million-token Swin GEMMs use 128-row tiles
     // (few rows but tens of thousands of output channels -- the input gradient of the 37632 -> 512 embedding head: there are
-    //  workgroups enough, 128-row tiles read each weight slab half as often; FMMT_NT_WIDE64=1 keeps the 64-row tiles for it)
-    static const int wide64 = fmmt_const("FMMT_NT_WIDE64", 0);
-    if (a.M <= 4096 && (a.N < 16384 || a.M < 256 || wide64)) {
+    //  workgroups enough, 128-row tiles read each weight slab half as often)
+    if (a.M <= 4096 && (a.N < 16384 || a.M < 256)) {
         if constexpr (sizeof(T) == 2) {
             // Fewer 64 x 128 tiles than half the CUs (the fusion stack: 152-1328 tokens x 768 channels = 18-126 tiles): such a
             // launch is a chain of K / 64 steps whose cost is the step's DMA issue (six 1-KB pieces per wave) plus a barrier, on a
@@ -1233,18 +1179,12 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             // wave and step.  Measured per launch inside a graph (tools/probes/few_probe.py, same call): 152-640 x 768 x 768 8.5 -> 5.5 us
             // (hipBLASLt 7.5-8.1), 1328 x 768 x 768 9.2 -> 6.7, 664 x 1536 x 768 9.0 -> 6.5, 512 x 3072 x 768 12.9 -> 9.8,
             // 512 x 768 x 3072 24.4 -> 16, 1328 x 768 x 3072 25.5 -> 19.5; with 256+ tiles of 64 x 128 the quarter tiles lose
-            // (1328 x 3072 x 768: 14 -> 22 us), and the four-buffer ring does nothing for K = 768.
-            // FMMT_NT_SMALL: 1 (default) = 32 x 64, 2 = 64 x 64 (6.4 us on the first group), 0 = off.
-            static const int small = fmmt_const("FMMT_NT_SMALL", 1);
+            // (1328 x 3072 x 768: 14 -> 22 us), and the four-buffer ring does nothing for K = 768.  (64 x 64 tiles: 6.4 us on the first group.)
+            constexpr int SMALL_TILES = 256;               // quarter tiles below this many 64 x 128 tiles
+            constexpr int SMALL_R4K = 2048;                // four-buffer ring from this K
             const int tiles = ((a.M + 63) / 64) * ((a.N + 127) / 128);
-            static const int small_tiles = fmmt_const("FMMT_NT_SMALL_TILES", 256);
-            static const int small_r4k = fmmt_const("FMMT_NT_SMALL_R4K", 2048);
-            if (small && tiles < small_tiles && a.N % 64 == 0 && a.K % 64 == 0 && a.K >= 128 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
-                if (small == 2) {
-                    if (a.K >= 2048 && 2 * tiles <= 256) return launch_nt<T, 64, 64, 64, 4, true>(a, st);
-                    return launch_nt<T, 64, 64, 64, 2, true>(a, st);
-                }
-                if (a.K >= small_r4k) return launch_nt<T, 32, 64, 64, 4, true>(a, st);
+            if (tiles < SMALL_TILES && a.N % 64 == 0 && a.K % 64 == 0 && a.K >= 128 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
+                if (a.K >= SMALL_R4K) return launch_nt<T, 32, 64, 64, 4, true>(a, st);
                 return launch_nt<T, 32, 64, 64, 2, true>(a, st);
             }
         }
@@ -1257,24 +1197,16 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             if (ph == 4) return epi3 == 6 ? launch_ph3<6, true, 4>(a, st) : epi3 == 5 ? launch_ph3<5, true, 4>(a, st) : launch_ph3<2, true, 4>(a, st);
             return epi3 == 3 ? launch_ph3<3>(a, st) : epi3 == 6 ? launch_ph3<6>(a, st) : epi3 == 5 ? launch_ph3<5>(a, st) : launch_ph3<2>(a, st);
         }
-        if (const int bn = p256_plan(a)) {
-            // FMMT_NT_P256_RING: 1 (default) = K step 64, ring of 2 (3 for 128-wide tiles); 0 = K step 32, ring of 4.
-            // Measured (profiles/r02_gemm_shapes.txt): the K-step-64 form wins on every shape by 3-17 % (half the barriers)
-            static const int ring = fmmt_const("FMMT_NT_P256_RING", 1);
-            if (ring == 0 || a.K % 64) return bn == 256 ? launch_p256<256, 32, 4>(a, st) : bn == 192 ? launch_p256<192, 32, 4>(a, st) : launch_p256<128, 32, 4>(a, st);
+        if (const int bn = p256_plan(a))
             return bn == 256 ? launch_p256<256, 64, 2>(a, st) : bn == 192 ? launch_p256<192, 64, 2>(a, st) : launch_p256<128, 64, 3>(a, st);
-        }
         // measured (tools/probes/gemm_bench.py): +8 % on the 125440-token stage-2 shapes (K = 384: 496 -> 540 TF/s),
         // -4 % on the 31360-token stage-3 shapes (tile quantisation at one workgroup per CU) -> only for M >= 65536
-        static const int deep = fmmt_const("FMMT_NT_DEEP", 1);
-        static const int deep_mink = fmmt_const("FMMT_NT_DEEP_MINK", 96);
-        static const int deep96 = fmmt_const("FMMT_NT_DEEP96", 1);
+        constexpr int DEEP_MINM = 65536, DEEP_MINK = 96;
         // K = 96 (stage 0, three K steps): -5..7 % with the deep kernel except for the GELU + pre-activation launch
         // (two output streams; measured +2 %), which keeps the single-step kernel
-        static const int deep_minm = fmmt_const("FMMT_NT_DEEP_MINM", 65536);
-        const bool big = deep && a.M >= deep_minm && !a.ksplit && a.K % 32 == 0 && a.K >= deep_mink && a.ldx % 8 == 0 && a.ldw % 8 == 0 &&
+        const bool big = a.M >= DEEP_MINM && !a.ksplit && a.K % 32 == 0 && a.K >= DEEP_MINK && a.ldx % 8 == 0 && a.ldw % 8 == 0 &&
                          !(a.K == 96 && a.epi == FMMT_EPI_GELU);
-        if (big && (a.N % 128 == 0 || (n96 && deep96)) && (a.K % 64 == 0 || deep == 1 || deep == 2)) {
+        if (big && (a.N % 128 == 0 || n96)) {
             constexpr size_t lds = (size_t)3 * (256 + 128) * 64 * 2;
             constexpr size_t lds96 = (size_t)3 * (256 + 96) * 32 * 2;
             static FmmtLdsOnce lds_once[7];
@@ -1292,10 +1224,7 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             }
             LinArgs p = a;
             p.tiles_m = (a.M + 255) / 256;
-            static const int slab = fmmt_const("FMMT_NT_SLAB", 1);
-            static const int wslab = fmmt_const("FMMT_NT_WSLAB", 1);
-            p.reserved = (slab ? 0 : 16) | (wslab ? 0 : 32);
-            if (n96) {
+                    if (n96) {
                 p.tiles_n = a.N / 96;
                 if (a.K == 192) hipLaunchKernelGGL((linear_nt_deep32_kernel<6, 96>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds96, st, p);
                 else if (a.K == 96) hipLaunchKernelGGL((linear_nt_deep32_kernel<3, 96>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds96, st, p);
@@ -1307,8 +1236,7 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             // measured (tools/probes/gemm_bench.py, 125440 tokens): the K-step-32 kernel with two workgroups per CU wins
             // where the epilogue is a large share of a tile's life -- GELU / GELU' launches (0.388 -> 0.340 ms) and
             // K = 384 (384x384: 0.069 -> 0.057 ms); the K-step-64 kernel keeps a 2-4 % edge on plain K >= 1152.
-            // FMMT_NT_DEEP: 1 = this policy, 2 = always K step 32, 4 = always K step 64, 0 = 128-row kernels only
-            if (deep == 2 || (deep == 1 && (a.epi != 0 || a.K <= 512)) || a.K % 64 != 0) {
+            if (a.epi != 0 || a.K <= 512 || a.K % 64 != 0) {
                 if (a.K == 192) hipLaunchKernelGGL((linear_nt_deep32_kernel<6, 128>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds / 2, st, p);
                 else if (a.K == 96) hipLaunchKernelGGL((linear_nt_deep32_kernel<3, 128>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds / 2, st, p);
                 else hipLaunchKernelGGL((linear_nt_deep32_kernel<0, 128>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds / 2, st, p);
@@ -1365,25 +1293,11 @@ struct TnArgs {
     int tiles_k;
     int chunk;          // rows of m per split (multiple of the m step)
     int tiles_n;
-    int xcd;            // 1: chunked XCD remap of the (split, tile) work list
     int x_gelu;         // 1: the x operand holds a pre-activation; contract with gelu(x) (recomputed activation of the fused Mlp)
     int* hdr;           // workspace header: hdr[0] receives the number of splits written (read by the finish pass); may be NULL
     int splits;
     int npad;           // rows of one split's partials (stride of part_w / part_b); 0 = N.  > N: linear_tn_dma_kernel<384,192> on an N that is 192 short of a tile
 };
-
-__device__ __forceinline__ bf16x8 lds_tr_frag(const bf16* s, int pitch, int c0, int li, int lg) {
-    // 16-lane group lg covers token rows lg*8 .. lg*8+7; lane li supplies row (li>>2) (+4), column
-    // chunk (li&3)*4 and receives column li of the 4x16 block (4 tokens).
-    const bf16* a0 = s + (lg * 8 + (li >> 2)) * pitch + c0 + (li & 3) * 4;
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * pitch));
-    union { struct { s16x4 lo, hi; } s; bf16x8 v; } u;
-    u.s.lo = lo;
-    u.s.hi = hi;
-    return u.v;
-}
 
 // bf16 tiles of the TN kernel: unpadded 256-byte rows (128 channels) whose eight 32-byte column blocks are XOR-permuted by
 // g(row) = (row & 3) | ((row >> 3) & 1) << 2.  A ds_read_b64_tr_b16 serves lanes 0-31 in one LDS cycle: two 16-lane groups,
@@ -1432,7 +1346,7 @@ void linear_tn_kernel(TnArgs p) {
     // tiles are kept on one XCD (chunked XCD remap over the split-major work list): with the head-major order each
     // XCD's L2 fetched every operand slab again (FETCH_SIZE 1.9x the algorithmic bytes on the stage-2 launches).
     const int tiles = p.tiles_n * p.tiles_k;
-    const int logical = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int split = logical / tiles, tile = logical - split * tiles;
     const int tile_n = tile / p.tiles_k, tile_k = tile % p.tiles_k;
     const int n0 = tile_n * 128, k0 = tile_k * 128;
@@ -1755,7 +1669,7 @@ int launch_tn_few(int M, int N, int K, const void* dy, int lddy, const void* x, 
     constexpr int lds = 80 * 1024;
     static FmmtLdsOnce lds_once;
     if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_few_kernel), lds)) return rc_;
-    TnArgs a{M, N, K, dy, lddy, x, ldx, dw, db, nullptr, 1, K / 64, (M + 7) / 8, N / 64, 0, 0, hdr, 1};
+    TnArgs a{M, N, K, dy, lddy, x, ldx, dw, db, nullptr, 1, K / 64, (M + 7) / 8, N / 64, 0, hdr, 1};
     hipLaunchKernelGGL(linear_tn_few_kernel, dim3((N / 64) * (K / 64)), dim3(512), lds, st, a);
     FMMT_CHECK_LAUNCH();
     return 0;
@@ -1763,10 +1677,9 @@ int launch_tn_few(int M, int N, int K, const void* dy, int lddy, const void* x, 
 
 // eligibility of linear_tn_few_kernel: bf16, 129..2048 tokens, whole 64 x 64 tiles, at least 8 of them, 16-byte rows
 bool tn_few_ok(int M, int N, int K, int dtype) {
-    static const int on = fmmt_const("FMMT_TN_FEW", 1);
     // (at most 1024 tiles: the embedding head's 512 x 37632 gradient -- 4704 tiles of 640 tokens -- took 767 us here against 292 us
     //  with the 128 x 128-tile kernel, whose workgroups reuse each staged token slab four times as often)
-    return on && dtype == FMMT_BF16 && M > 128 && M <= 2048 && N % 64 == 0 && K % 64 == 0 && (N / 64) * (K / 64) >= 8 && (N / 64) * (K / 64) <= 1024;
+    return dtype == FMMT_BF16 && M > 128 && M <= 2048 && N % 64 == 0 && K % 64 == 0 && (N / 64) * (K / 64) >= 8 && (N / 64) * (K / 64) <= 1024;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1855,7 +1768,7 @@ __global__ __launch_bounds__(512) void linear_tn_dma_kernel(TnArgs p) {
     const int wn = wave / WK, wk = wave % WK;
     const int li = lane & 15, lg = lane >> 4;
     const int tiles = p.tiles_n * p.tiles_k;
-    const int logical = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int logical = xcd_remap(blockIdx.x, gridDim.x);
     const int split = logical / tiles, tile = logical - split * tiles;
     const int tile_n = tile / p.tiles_k, tile_k = tile % p.tiles_k;
     const int n0 = tile_n * TNn, k0 = tile_k * TKk;
@@ -2308,7 +2221,7 @@ extern "C" int fmmt_linear_fwd(int dtype, int M, int N, int K,
     if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (bias && !aligned16(bias)) ||
         (res && !aligned16(res)) || (aux && !aligned16(aux)) || (y_pre && !aligned16(y_pre)))
         return FMMT_EALIGN;
-    LinArgs a{M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, 0, 0, 1, 0, nullptr};
+    LinArgs a{M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, 0, 0, 0, 0, nullptr};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     return dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st) : dispatch_nt<float>(a, st);
 }
@@ -2328,7 +2241,7 @@ extern "C" int fmmt_linear_fwd_seg3(int dtype, int M, int N, int K, const void* 
     if (seg_mode == 2 && (bias0 || bias1 || bias2)) return FMMT_EINVAL;
     if (!aligned16(x) || !aligned16(w0) || !aligned16(w1) || !aligned16(w2) || !aligned16(y)) return FMMT_EALIGN;
     if (((M + 63) / 64) * ((N + 127) / 128) >= 256) return FMMT_EINVAL;                 // dispatch_nt's few-tile rule: larger problems do not come here
-    LinArgs a{M, N, K, x, ldx, w0, ldw, bias0, y, ldy, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 1, 0, nullptr};
+    LinArgs a{M, N, K, x, ldx, w0, ldw, bias0, y, ldy, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, 0, nullptr};
     a.w1 = w1;
     a.w2 = w2;
     a.bias1 = bias1;
@@ -2358,7 +2271,7 @@ extern "C" int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void
     const int splits = splitk_plan(M, N, K, &ks);
     if (!ks) return FMMT_EINVAL;                            // not a split-K shape: use fmmt_linear_fwd
     if (workspace_bytes < (size_t)splits * M * N * sizeof(float)) return FMMT_EWORKSPACE;
-    LinArgs a{M, N, K, x, ldx, w, ldw, nullptr, nullptr, N, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 1, ks,
+    LinArgs a{M, N, K, x, ldx, w, ldw, nullptr, nullptr, N, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, ks,
               reinterpret_cast<float*>(workspace)};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (int rc = (dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st) : dispatch_nt<float>(a, st))) return rc;
@@ -2375,16 +2288,15 @@ namespace {
 // DMA-staged plan (linear_tn_dma_kernel): tile TNn x 128 with TNn = 256 / 192, one workgroup per CU, splits = 256 / tiles
 TnPlan tn_plan_dma(int M, int N, int K) {
     TnPlan pl{0, 0, 0, 0, 0, 0, 0, 0};
-    // Default on (FMMT_TN_DMA=0: everything register-staged).  History: the first version of this kernel (256 / 192 x 128 tiles,
+    // History: the first version of this kernel (256 / 192 x 128 tiles,
     // the builtin ds_read_tr) measured 3-9 % SLOWER than the register-staged kernel with 68 % of its wave cycles parked in
     // waits -- hipcc had put s_waitcnt vmcnt(0) in front of every stage's first fragment read, so the ring never had a second
     // stage in flight.  With the reads in inline asm, 128 FLOP per staged byte and four 32-token stages: 860-1105 TF/s against
     // 550-630.
-    static const int mode = fmmt_const("FMMT_TN_DMA", 1);
-    // FMMT_TN_DMA_MINM: fewest tokens for this kernel, exclusive.  8192 since the 320-frame legs (configs[4]: 15680 stage-3 tokens)
+    // Fewest tokens for this kernel, exclusive.  8192 since the 320-frame legs (configs[4]: 15680 stage-3 tokens)
     // measured 56.2 -> 55.7 ms per step with it, three alternating pairs in one call; 16384 before.
-    static const int minm = fmmt_const("FMMT_TN_DMA_MINM", 8192);
-    if (!mode || M <= minm || M % 64) return pl;
+    constexpr int TN_DMA_MINM = 8192;
+    if (M <= TN_DMA_MINM || M % 64) return pl;
     int tn = 0, tk = 0;
     if (N % 256 == 0 && K % 256 == 0) tn = 256, tk = 256;
     else if (N % 192 == 0 && K % 384 == 0) tn = 192, tk = 384;
@@ -2446,17 +2358,15 @@ namespace {
 // the split contraction: part_w [splits][N][K], part_b [splits][N] or nullptr (splits == 1: these may be dw / db themselves)
 int launch_tn_plan(int dtype, int M, int N, int K, const void* dy, int lddy, const void* x, int ldx, float* part_w, float* part_b,
                    const float* rowscale, int rows_per_scale, int x_epi, int* hdr, hipStream_t st) {
-    static const int tn_xcd = fmmt_const("FMMT_TN_XCD", 1);
     if (x_epi != 0 && x_epi != FMMT_EPI_GELU) return FMMT_EINVAL;
     if (tn_few_ok(M, N, K, dtype) && !rowscale && !x_epi && lddy % 8 == 0 && ldx % 8 == 0)
         return launch_tn_few(M, N, K, dy, lddy, x, ldx, part_w, part_b, hdr, st);     // one split: part_w / part_b may be dw / db themselves
     if (dtype == FMMT_BF16 && hdr && !x_epi && lddy % 8 == 0 && ldx % 8 == 0) {
         const TnPlan pd = tn_plan_dma(M, N, K);
         // scaled launches: the split's slice of the scale vector has to fit the 4 KB behind the ring
-        static const int dma_scaled = fmmt_const("FMMT_TN_DMA_SCALED", 1);
-        const bool scaled_ok = !rowscale || (dma_scaled && rows_per_scale >= 32 && pd.tn && pd.tk != 192 && pd.chunk / rows_per_scale + 2 <= 1024);
+        const bool scaled_ok = !rowscale || (rows_per_scale >= 32 && pd.tn && pd.tk != 192 && pd.chunk / rows_per_scale + 2 <= 1024);
         if (pd.tn && scaled_ok) {
-            TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pd.tiles_k, pd.chunk, pd.tiles_n, tn_xcd, 0, hdr, pd.splits, pd.npad};
+            TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pd.tiles_k, pd.chunk, pd.tiles_n, 0, hdr, pd.splits, pd.npad};
             const int grid = pd.tiles_n * pd.tiles_k * pd.splits;
             if (rowscale) return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2, true>(a, grid, st) : launch_tn_dma<192, 384, 4, 2, true>(a, grid, st);
             if (pd.tk == 192) return launch_tn_dma<384, 192, 4, 4>(a, grid, st);
@@ -2464,21 +2374,16 @@ int launch_tn_plan(int dtype, int M, int N, int K, const void* dy, int lddy, con
         }
     }
     const TnPlan pl = tn_plan(M, N, K, dtype);
-    TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pl.tiles_k, pl.chunk, pl.tiles_n, tn_xcd, x_epi == FMMT_EPI_GELU, hdr, pl.splits};
+    TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pl.tiles_k, pl.chunk, pl.tiles_n, x_epi == FMMT_EPI_GELU, hdr, pl.splits};
     dim3 grid(pl.tiles_n * pl.tiles_k * pl.splits);
-    static const int tn_cfg = fmmt_const("FMMT_TN_CFG", 0);
-    // measured (tools/probes/gemm_bench.py): 64-token steps win for the compute-heavy stage-2/3 shapes (+15-25 %),
-    // 32-token steps (3 workgroups per CU) win for the HBM-bound multi-million-token stage-0/1 shapes
-    const bool bms64 = tn_cfg == 2 || (tn_cfg == 0 && M <= 262144);
-    // two token steps in flight (register sets R0/R1): measured +3..5 % on the stage-2/3 shapes, +3..11 % on the stage-0/1
-    // ones, at unchanged occupancy (200 / 160 registers); FMMT_TN_PF=1 selects the single-step prefetch
-    static const int tn_pf = fmmt_const("FMMT_TN_PF", 3);
     if (dtype == FMMT_BF16) {
-        // few-token problems: FMMT_TN_FEW64=1 (A/B switch) takes 64-token steps with two register sets in flight
-        static const int few64 = fmmt_const("FMMT_TN_FEW64", 0);
-        if (M <= 4096) return few64 ? launch_tn<bf16, 64, true, 2>(a, grid, st) : launch_tn<bf16, 32, true>(a, grid, st);
-        if (bms64) return tn_pf >= 2 ? launch_tn<bf16, 64, false, 2>(a, grid, st) : launch_tn<bf16, 64>(a, grid, st);
-        return tn_pf >= 3 ? launch_tn<bf16, 32, false, 2>(a, grid, st) : launch_tn<bf16, 32>(a, grid, st);
+        if (M <= 4096) return launch_tn<bf16, 32, true>(a, grid, st);      // few-token problems: 32-token steps, one in flight
+        // measured (tools/probes/gemm_bench.py): 64-token steps win for the compute-heavy stage-2/3 shapes (+15-25 %),
+        // 32-token steps (3 workgroups per CU) win for the HBM-bound multi-million-token stage-0/1 shapes.
+        // Two token steps in flight (register sets R0/R1): measured +3..5 % on the stage-2/3 shapes, +3..11 % on the stage-0/1
+        // ones, at unchanged occupancy (200 / 160 registers)
+        if (M <= 262144) return launch_tn<bf16, 64, false, 2>(a, grid, st);
+        return launch_tn<bf16, 32, false, 2>(a, grid, st);
     }
     return launch_tn<float, 16>(a, grid, st);
 }

@@ -18,7 +18,8 @@ struct LinArgs {
     const void* res; int ldres;
     const float* rowscale; int rows_per_scale;
     int tiles_n, tiles_m;
-    int reserved;      // launcher-to-kernel A/B bits: 4 direct p256 epilogue, 8 no GELU slab, 16 no block slab, 32 no wave slab
+    int chan_rows;     // always 0.  Read by linear_nt_p256_kernel's operand-prefetch (HASOP) instantiations alone, where it would select weight rows in channel
+                       // order: with that choice folded at compile time those kernels measured ~1 % slower on their scale-only launches (register allocation), twice
     int ksplit;        // K range per blockIdx.y (split-K); 0 = no split
     float* part;       // split-K: fp32 partials [split][M][N] instead of the epilogue
     // Segmented weight operand (fmmt_linear_fwd_seg3; few-token direct-to-LDS kernels only): wseg_mode 1 = along N (output channels

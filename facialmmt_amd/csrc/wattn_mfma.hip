@@ -37,7 +37,7 @@ __device__ __forceinline__ void fill_bias_mfma(const WaArgs& p, int head, float*
 // blockIdx -> (head, window group).  The hardware places block b on XCD b % 8, and each XCD has its own L2.  A head
 // slice of a token is 64 B, half an L2 line, so the heads of one window group should run on the SAME XCD at about the
 // same time: with groups_per_head a multiple of 8 (the launcher rounds it), blocks are numbered
-// b = (grp / 8) * 8 * nH + head * 8 + grp % 8, i.e. b % 8 == grp % 8 for every head.  (FMMT_WA_XCD=0: head-major.)
+// b = (grp / 8) * 8 * nH + head * 8 + grp % 8, i.e. b % 8 == grp % 8 for every head.
 __device__ __forceinline__ void head_group_of_block(const WaArgs& p, int& head, int& grp) {
     const int b = blockIdx.x;
     if (p.xcd_grouped) {

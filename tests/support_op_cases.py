@@ -85,8 +85,8 @@ def t_linear():
 
 
 def t_linear_large():
-    """many-token bf16 problems (>= 65536 rows: the 256-row deep-pipelined kernels; FMMT_NT_DEEP selects the
-    variant) with ragged M, every epilogue, against fp32 torch matmuls of the same bf16 operands"""
+    """many-token bf16 problems (>= 65536 rows: the 256-row deep-pipelined kernels, K step 32 or 64 by epilogue
+    and K) with ragged M, every epilogue, against fp32 torch matmuls of the same bf16 operands"""
     dt, tol = torch.bfloat16, 2e-2
     for (M, N, K) in [(65536 + 77, 384, 384), (70000, 1536, 384), (65536, 384, 1536), (66000, 128, 256), (65600, 768, 192),
                       (65536 + 77, 192, 192), (70000, 576, 192), (65600, 96, 384), (65536, 96, 288), (66000, 288, 768),
@@ -151,9 +151,7 @@ def t_wgrad_large():
     """many-token bf16 weight gradients (ragged token counts, bias gradient, DropPath row scale with a dropped sample) against fp32
     torch matmuls of the same bf16 operands (both sides accumulate exact products in fp32).  The unscaled launches of the
     stage-2/3 shapes take the DMA-staged kernel (256x256 / 192x384 tiles, bias gradient through the ones-fragment MFMA), the
-    scaled ones and the other shapes the register-staged kernel.  (FMMT_TN_DMA=0 sends everything to the register-staged kernel, but
-    fmmt_const reads the variable once per process: tests/test_gpu_ops.py runs the list with the default only; the other setting needs a
-    process of its own, e.g. `FMMT_TN_DMA=0 python tests/support_op_cases.py`.)"""
+    scaled ones and the other shapes the register-staged kernel."""
     dt, tol = torch.bfloat16, 1e-3
     for (M, N, K) in [(125440, 1536, 384), (125440, 384, 1536), (125440, 1152, 384), (125440, 384, 384), (31360, 768, 768),
                       (20008, 1536, 384), (17000, 384, 1536), (31360, 2304, 768), (501760, 192, 384), (62720, 768, 384),

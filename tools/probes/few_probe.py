@@ -1,8 +1,11 @@
 """Development aid: the few-token NT launches of the fusion stack (152-1328 tokens x 768 / 3072 channels) alone, GPU time per launch from
-a captured graph of 20 launches, with a value check against torch (A/B of FMMT_NT_SMALL: one process per setting, same gpurun call)."""
+a captured graph of 20 launches, with a value check against torch (A/B of two builds: one process per library through PROBE_LIB, same call)."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from facialmmt_amd import _lib
+if os.environ.get("PROBE_LIB"):                                # A/B of two builds in one call
+    _lib.LIB_PATH = os.environ["PROBE_LIB"]
 from facialmmt_amd import ops
 from facialmmt_amd._lib import EPI_GELU, EPI_GELU_BWD
 dev = torch.device("cuda:0")
@@ -39,5 +42,5 @@ for (M, N, K) in [(152, 768, 768), (166, 768, 768), (512, 768, 768), (640, 768, 
     t = graph_time(lambda: ops.linear_raw(x, w, b)); tot += t
     t2 = graph_time(lambda: ops.linear_raw(x, w, b, res=res)); tot += t2
     print(f"  {M:6d}x{N:5d}x{K:5d}: nt {t*1e6:6.1f} us | +res {t2*1e6:6.1f} us | max err {e:.4f} {'ok' if ok else 'BAD'}", flush=True)
-print(f"  total {tot*1e6:.1f} us  bad {bad}  FMMT_NT_SMALL={os.environ.get('FMMT_NT_SMALL', '')}")
+print(f"  total {tot*1e6:.1f} us  bad {bad}  lib {os.path.basename(_lib.LIB_PATH)}")
 sys.exit(1 if bad else 0)

@@ -17,7 +17,7 @@ SHAPES_ALL = [(2007040, 288, 96), (2007040, 96, 96), (2007040, 384, 96), (200704
 SHAPES = [sh for sh in SHAPES_ALL if not os.environ.get("GEMM_BENCH_M") or sh[0] == int(os.environ["GEMM_BENCH_M"])]
 if os.environ.get("GEMM_BENCH_FEW"):
     SHAPES = []
-print("cfg", os.environ.get("FMMT_NT_CFG", "0"))
+print("lib", os.path.basename(_lib.LIB_PATH))
 from facialmmt_amd._lib import EPI_GELU, EPI_GELU_BWD
 tot = 0
 for (M, N, K) in SHAPES:

@@ -1,5 +1,5 @@
-"""Development aid: the many-token NT launches of Swin stages 1-3 alone, timed with HIP events (A/B of the FMMT_NT_* switches: one
-process per setting, same gpurun call); --vendor adds hipBLASLt (torch.nn.functional.linear) on the same operands."""
+"""Development aid: the many-token NT launches of Swin stages 1-3 alone, timed with HIP events (A/B of two builds: one
+process per library through PROBE_LIB, same call); --vendor adds hipBLASLt (torch.nn.functional.linear) on the same operands."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -54,4 +54,4 @@ for (M, N, K) in SHAPES:
         tv = ev(lambda: torch.nn.functional.linear(x, w))
         line += f" || hipblaslt {tv*1e3:7.1f} us {2.0*M*N*K/tv/1e9:6.1f} TF/s"
     print(line, flush=True)
-print(f"  total {tot*1e3:.1f} us   FMMT_NT_P256_BATCH={os.environ.get('FMMT_NT_P256_BATCH', '')} RING={os.environ.get('FMMT_NT_P256_RING', '')} OPS={os.environ.get('FMMT_NT_P256_OPS', '')}")
+print(f"  total {tot*1e3:.1f} us   lib {os.path.basename(_lib.LIB_PATH)}")

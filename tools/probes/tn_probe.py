@@ -1,5 +1,5 @@
-"""Development aid: the stage-2/3 weight-gradient launches alone, timed with HIP events (A/B of the FMMT_TN_* switches: one
-process per setting, same gpurun call), or bare for PMC passes (rocprofv3 --pmc ... -- python tools/probes/tn_probe.py --bare)."""
+"""Development aid: the stage-2/3 weight-gradient launches alone, timed with HIP events (A/B of two builds: one
+process per library through PROBE_LIB, same call), or bare for PMC passes (rocprofv3 --pmc ... -- python tools/probes/tn_probe.py --bare)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -55,4 +55,4 @@ for (M, N, K) in SHAPES:
     tot += bs
     print(f"  tn {M:7d}x{N:5d}x{K:5d}: partials {best*1e3:7.1f} us {2.0*M*N*K/best/1e9:6.1f} TF/s | with reduce {full*1e3:7.1f} us | DropPath-scaled partials {bs*1e3:7.1f} us {2.0*M*N*K/bs/1e9:6.1f} TF/s", flush=True)
 if not bare:
-    print(f"  total with reduce {tot*1e3:.1f} us   FMMT_TN_DMA={os.environ.get('FMMT_TN_DMA', '')}")
+    print(f"  total with reduce {tot*1e3:.1f} us   lib {os.path.basename(_lib.LIB_PATH)}")
