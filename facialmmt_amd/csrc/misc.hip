@@ -3,6 +3,7 @@
 // embedding (scale + sinusoidal position with the zero-is-padding rule) and an elementwise scale.
 #include "fmmt_common.h"
 #include "bn1d_core.h"
+#include "adamw_core.h"
 #include "../../include/fmmt.h"
 
 namespace {
@@ -301,83 +302,11 @@ __global__ __launch_bounds__(1024) void sumsq_finish_kernel(const float* __restr
     if (threadIdx.x == 0) out[0] = sqrtf(red[0]);
 }
 
-struct AdamDesc {
-    float* p; const void* g; float* m; float* v; bf16* low;     // low may be null
-    long long n;
-    int blk_begin, g_bf16;                                      // g_bf16: the gradient is bf16 (the twin's own .grad), else fp32
-};
+// the record (AdamDesc) and the body live in adamw_core.h, shared with the guarded update of guard.hip
 __global__ __launch_bounds__(256) void adamw_batch_kernel(const AdamDesc* __restrict__ desc, int n_desc, const float* __restrict__ lr_p,
                                                           const float* __restrict__ step_p, const float* __restrict__ norm_p,
                                                           float beta1, float beta2, float eps, float wd, float max_norm, int hf) {
-    int lo = 0, hi = n_desc - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (desc[mid].blk_begin <= (int)blockIdx.x) lo = mid;
-        else hi = mid - 1;
-    }
-    const AdamDesc d = desc[lo];
-    const float lr = *lr_p, t = *step_p;
-    const float coef = norm_p ? fminf(1.0f, max_norm / (*norm_p + 1e-6f)) : 1.0f;
-    const float bc1 = 1.0f - powf(beta1, t), bc2s = sqrtf(1.0f - powf(beta2, t));
-    const float step_size = hf ? lr * bc2s / bc1 : lr / bc1, decay = hf ? 1.0f : 1.0f - lr * wd;
-    const float den_div = hf ? 1.0f : bc2s, post = hf ? -lr * wd : 0.0f;
-    const long long base = (long long)((int)blockIdx.x - d.blk_begin) * 4096;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const long long o = base + (long long)(i * 256 + threadIdx.x) * 4;
-        if (o >= d.n) break;
-        const float* gf = reinterpret_cast<const float*>(d.g);
-        const bf16* gb = reinterpret_cast<const bf16*>(d.g);
-        const bool g_ok = d.g_bf16 ? (reinterpret_cast<uintptr_t>(gb + o) & 7) == 0 : (reinterpret_cast<uintptr_t>(gf + o) & 15) == 0;
-        if (o + 4 <= d.n && g_ok && ((reinterpret_cast<uintptr_t>(d.p + o) | reinterpret_cast<uintptr_t>(d.m + o) |
-                                       reinterpret_cast<uintptr_t>(d.v + o)) & 15) == 0) {
-            f32x4 p = *reinterpret_cast<const f32x4*>(d.p + o), g;
-            if (d.g_bf16) {
-                const bf16x4 t = *reinterpret_cast<const bf16x4*>(gb + o);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) g[e] = (float)t[e];
-            } else {
-                g = *reinterpret_cast<const f32x4*>(gf + o);
-            }
-            f32x4 m = *reinterpret_cast<const f32x4*>(d.m + o), v = *reinterpret_cast<const f32x4*>(d.v + o);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float ge = g[e] * coef;
-                p[e] *= decay;
-                m[e] = beta1 * m[e] + (1.0f - beta1) * ge;
-                v[e] = beta2 * v[e] + (1.0f - beta2) * ge * ge;
-                p[e] -= step_size * (m[e] / (sqrtf(v[e]) / den_div + eps));
-                p[e] = fmaf(p[e], post, p[e]);
-            }
-            *reinterpret_cast<f32x4*>(d.p + o) = p;
-            *reinterpret_cast<f32x4*>(d.m + o) = m;
-            *reinterpret_cast<f32x4*>(d.v + o) = v;
-            if (d.low) {
-                if ((reinterpret_cast<uintptr_t>(d.low + o) & 7) == 0) {
-                    bf16x4 l;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) l[e] = (bf16)p[e];
-                    *reinterpret_cast<bf16x4*>(d.low + o) = l;
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) d.low[o + e] = (bf16)p[e];
-                }
-            }
-        } else {
-            for (long long j = o; j < d.n && j < o + 4; ++j) {
-                const float ge = (d.g_bf16 ? (float)gb[j] : gf[j]) * coef;
-                float p = d.p[j] * decay;
-                const float m = beta1 * d.m[j] + (1.0f - beta1) * ge;
-                const float v = beta2 * d.v[j] + (1.0f - beta2) * ge * ge;
-                p -= step_size * (m / (sqrtf(v) / den_div + eps));
-                p = fmaf(p, post, p);
-                d.p[j] = p;
-                d.m[j] = m;
-                d.v[j] = v;
-                if (d.low) d.low[j] = (bf16)p;
-            }
-        }
-    }
+    adamw_batch_body<false>(desc, n_desc, lr_p, step_p, norm_p, beta1, beta2, eps, wd, max_norm, hf);
 }
 
 // LayerNorm backward for a bf16 module with bf16 affine parameters (the text encoder's 49 LayerNorms: torch's own backward is

@@ -348,6 +348,36 @@ def adamw_batch(n, blocks, desc, lr, step, total_norm, beta1, beta2, eps, weight
                                        float(weight_decay), float(max_norm), 1 if hf else 0, _st()), "fmmt_adamw_batch")
 
 
+def adamw_batch_guarded(n, blocks, desc, lr, step, total_norm, beta1, beta2, eps, weight_decay, max_norm, hf=False):
+    """fmmt_adamw_batch_guarded: adamw_batch that touches nothing when `total_norm` (required) holds a NaN or an inf.  `step` is the update count
+    BEFORE this update and is only read -- guard_commit, behind it on the same stream, advances it; on a finite norm the bits are adamw_batch's
+    with the step word one higher"""
+    if total_norm is None:
+        raise ValueError("adamw_batch_guarded: total_norm is what the guard decides on; it cannot be None")
+    check(_lib.load().fmmt_adamw_batch_guarded(n, blocks, _p(desc), _p(lr), _p(step), _p(total_norm), float(beta1), float(beta2), float(eps),
+                                               float(weight_decay), float(max_norm), 1 if hf else 0, _st()), "fmmt_adamw_batch_guarded")
+
+
+def _guard_words(words):
+    if words.dtype != torch.int64 or not words.is_contiguous() or words.numel() != _lib.GUARD_WORDS:
+        raise ValueError(f"words: a contiguous int64 tensor of {_lib.GUARD_WORDS} entries (include/fmmt_guard.h)")
+    return _p(words)
+
+
+def guard_commit(total_norm, step, words):
+    """fmmt_guard_commit, behind adamw_batch_guarded on the same stream: finite norm -> step += 1, applied += 1; else skipped += 1; last_norm = the
+    norm's bits (`words`: train_step.TrainMonitor's)"""
+    check(_lib.load().fmmt_guard_commit(_p(total_norm), _p(step), _guard_words(words), _st()), "fmmt_guard_commit")
+
+
+def monitor_loss(loss, scale, words):
+    """fmmt_monitor_loss: the fp32 device scalar `loss` times `scale` (the accumulation factor the step divided it by) into the monitor's double
+    sum when finite, counted as non-finite otherwise"""
+    if loss.dtype != torch.float32 or loss.numel() != 1:
+        raise ValueError("monitor_loss: one float32 value on the device")
+    check(_lib.load().fmmt_monitor_loss(_p(loss), float(scale), _guard_words(words), _st()), "fmmt_monitor_loss")
+
+
 class VendorLinearFn(torch.autograd.Function):
     """y = x W^T + b with the vendor library's GEMMs (torch.nn.functional.linear / matmul) and fmmt_colsum for the bias gradient:
     the text encoder's Linear layers (few thousand tokens: hipBLASLt's ground; its autograd formula spends a memset and a

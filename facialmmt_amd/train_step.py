@@ -951,12 +951,63 @@ class FusedHandOver:
         return True
 
 
+# GUARD_NOTE.  `skip_nonfinite=True` on a graphed training step (default False: nothing changes): the step builds a TrainMonitor (`step.monitor`), counts
+# every micro-step's loss in it behind the loss inside the captured forward/backward, and SKIPS an update whose gradient norm is NaN or infinite --
+# parameters, moments, bf16 twins and the update count keep their bits, the flat buffers are zeroed as after any update, `monitor.read().skipped`
+# counts it (FusedClipAdamW, FlatGradientTail; ValueError with an optimizer the fused update does not take).  The learning-rate schedule advances on a
+# skipped update too: that is what the reference does under GradScaler (train.py:139-143), and the host cannot know otherwise.  A non-finite FORWARD
+# is not undone (BatchNorm's running statistics in the auxiliary step): `monitor.read().nonfinite_losses` reports it.  The counters are diagnostics,
+# not part of state_dict(): they start at zero after a resume.
+class TrainMonitor:
+    """What a captured training run reports without a host synchronisation per step: six int64 words on the device (include/fmmt_guard.h,
+    _lib.GUARD_*) that ops.monitor_loss (once per micro-step, behind the loss) and ops.guard_commit (once per update) write.  `read()` is one
+    device-to-host copy; `reset()` zeroes in place (the captured graphs keep writing to this tensor).  The counters are diagnostics: they are
+    not part of a step's state_dict() and start at zero after a resume."""
+
+    def __init__(self, device="cuda"):
+        from . import _lib
+        self.words = torch.zeros(_lib.GUARD_WORDS, dtype=torch.int64, device=device)
+
+    def reset(self):
+        self.words.zero_()
+
+    @staticmethod
+    def summarise(host_words):
+        """the host half of read(): `host_words` = the six int64 words as copied from the device.  avg_loss: the mean of the finite micro-step
+        losses, undivided by the accumulation factor (what the reference logs, train.py:144-150), NaN while there is none; last_norm: the
+        gradient norm the last update saw, NaN or inf when it was skipped for it"""
+        import numpy as np
+        from . import _lib
+        host = np.ascontiguousarray(host_words, dtype=np.int64)
+        if host.shape != (_lib.GUARD_WORDS,):
+            raise ValueError(f"TrainMonitor.summarise: {_lib.GUARD_WORDS} int64 words")
+        loss_sum = float(host[_lib.GUARD_LOSS_SUM:_lib.GUARD_LOSS_SUM + 1].view(np.float64)[0])
+        micro = int(host[_lib.GUARD_MICRO_STEPS])
+        last_norm = float(host[_lib.GUARD_LAST_NORM:_lib.GUARD_LAST_NORM + 1].astype(np.uint32).view(np.float32)[0])
+        return types.SimpleNamespace(avg_loss=loss_sum / micro if micro else float("nan"), loss_sum=loss_sum, micro_steps=micro,
+                                     nonfinite_losses=int(host[_lib.GUARD_NONFINITE_LOSSES]), applied=int(host[_lib.GUARD_APPLIED]),
+                                     skipped=int(host[_lib.GUARD_SKIPPED]), last_norm=last_norm)
+
+    def read(self):
+        return self.summarise(self.words.cpu().numpy())
+
+    def loss(self, loss, scale):
+        """count one micro-step's loss (fp32 device scalar, already divided by `scale`): one launch, capture-safe"""
+        from . import ops
+        ops.monitor_loss(loss if loss.dtype == torch.float32 else loss.float(), scale, self.words)
+
+
 class FusedClipAdamW:
     """clip_grad_norm_ + AdamW.step() (torch.optim.AdamW, or HFAdamW = the reference's transformers.AdamW) (+ the bf16 re-rounding of parameters stepped through fp32 masters) as one
     multi-tensor norm and ONE kernel launch (fmmt_adamw_batch): the gradients are read once and not scaled in place, the fp32
     parameters are not read a second time for their bf16 twins.  Takes its hyper-parameters from an existing torch AdamW
     (one parameter group, tensor learning rate on the device as `capturable=True` keeps it, so a LambdaLR scheduler keeps
-    working); keeps its own moments and step counter -- `optimizer.state` stays empty while this is in use."""
+    working); keeps its own moments and step counter -- `optimizer.state` stays empty while this is in use.
+    `monitor` (a TrainMonitor; None: the path above, unchanged): the update is SKIPPED when the gradient norm is NaN or infinite -- what GradScaler
+    does for the reference under AMP (train.py:139-143) -- decided on the device: update() runs the norm, ops.adamw_batch_guarded (every block
+    reads the norm first and leaves p, m, v and the bf16 twins alone when it is not finite) and ops.guard_commit (advances `step` only for an
+    applied update, counts applied / skipped in the monitor).  `step` stays the number of APPLIED updates, so export() / load_from() mean what
+    they meant; with finite gradients every bit is the unguarded path's."""
 
     @staticmethod
     def eligible(opt, params):
@@ -966,8 +1017,9 @@ class FusedClipAdamW:
         return (torch.is_tensor(g["lr"]) and g["lr"].is_cuda and not g.get("amsgrad", False) and not g.get("maximize", False)
                 and g.get("correct_bias", True) and all(p.dtype == torch.float32 and p.is_cuda for p in params))
 
-    def __init__(self, opt, params, grad_of, low_of, max_norm):
+    def __init__(self, opt, params, grad_of, low_of, max_norm, monitor=None):
         import numpy as np
+        self.monitor = monitor
         g = opt.param_groups[0]
         self.lr, (self.b1, self.b2), self.eps, self.wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
         self.hf = isinstance(opt, HFAdamW)                    # transformers.AdamW's update (the reference's class) vs torch.optim.AdamW's
@@ -1045,7 +1097,8 @@ class FusedClipAdamW:
     @torch.no_grad()
     def update(self):
         from . import ops
-        self.step.add_(1.0)
+        if self.monitor is None:
+            self.step.add_(1.0)
         if not self.norm_ready:
             if self.norm_table is not None:
                 from . import _lib
@@ -1054,6 +1107,10 @@ class FusedClipAdamW:
             else:
                 self.norm.copy_(torch.nn.utils.get_total_norm(self.grads, 2.0, foreach=True))
         self.norm_ready = False
+        if self.monitor is not None:                          # `step` is the count before this update; the commit advances it when the update ran
+            ops.adamw_batch_guarded(self.n, self.blocks, self.desc, self.lr, self.step, self.norm, self.b1, self.b2, self.eps, self.wd, self.max_norm, self.hf)
+            ops.guard_commit(self.norm, self.step, self.monitor.words)
+            return
         ops.adamw_batch(self.n, self.blocks, self.desc, self.lr, self.step, self.norm, self.b1, self.b2, self.eps, self.wd, self.max_norm, self.hf)
 
 
@@ -1077,10 +1134,20 @@ class FlatGradientTail:
     gradients into them, and the update (clip + optimizer step).  The steps differ only in the forward/backward in front of it.
     `flat`: a GradientAverager(hooks=False), or the parameters to build one over; `masters`: MasterWeights of a sub-module that runs in bf16 --
     `flat` and the optimizer are then over the fp32 masters (step_parameters); `exchanging`: a gradient exchange runs between hand_over() and
-    update() (the caller's statement, read once: bool(flat.active) where the step exchanges); `capture_tables`: FusedHandOver's `captures`."""
+    update() (the caller's statement, read once: bool(flat.active) where the step exchanges); `capture_tables`: FusedHandOver's `captures`;
+    `monitor` (a TrainMonitor): the update is skipped on a non-finite gradient norm (FusedClipAdamW) -- only with the fused update: the stock
+    clip_grad_norm_ + opt.step() path cannot decide without a host synchronisation, so an optimizer FusedClipAdamW.eligible rejects is a
+    ValueError.  With accumulation a bad micro-step makes the window's buffers non-finite: the window's one update is skipped and update()
+    zeroes the buffers as always, so nothing of it reaches the next window."""
 
-    def __init__(self, flat, opt, clip, accumulate, masters=None, exchanging=False, capture_tables=4):
+    def __init__(self, flat, opt, clip, accumulate, masters=None, exchanging=False, capture_tables=4, monitor=None):
         from .parallel import GradientAverager
+        if not isinstance(flat, GradientAverager):
+            flat = list(flat)
+        if monitor is not None and not FusedClipAdamW.eligible(opt, flat.params if isinstance(flat, GradientAverager) else flat):
+            raise ValueError("skip_nonfinite needs the fused update (FusedClipAdamW.eligible: one group of torch.optim.AdamW / HFAdamW with a device "
+                             "learning rate over fp32 device parameters): the stock optimizer path cannot skip an update without a host synchronisation")
+        self.monitor = monitor
         self.opt, self.clip, self.accumulate, self.masters, self.exchanging = opt, clip, bool(accumulate), masters, bool(exchanging)
         self.flat = flat if isinstance(flat, GradientAverager) else GradientAverager(flat, hooks=False)
         self.flat_view_of = {p: p.grad for p in self.flat.params}          # the averager made every .grad a view of its bucket
@@ -1090,7 +1157,7 @@ class FlatGradientTail:
             l.grad = None
         self.fused = None
         if FusedClipAdamW.eligible(opt, self.flat.params):
-            self.fused = FusedClipAdamW(opt, self.flat.params, self.flat_view_of, low_of, clip)
+            self.fused = FusedClipAdamW(opt, self.flat.params, self.flat_view_of, low_of, clip, monitor=monitor)
         # hand-over and clip norm in one pass; with an exchange between the hand-over and the update (N > 1) the hand-over still runs as one pass, its norm is
         # discarded and FusedClipAdamW.update takes the norm of the REDUCED buffers in one more launch
         self.handover = FusedHandOver(len(self.pairs), captures=capture_tables) if (self.fused is not None and FUSED_HANDOVER) else None
@@ -1127,6 +1194,8 @@ class FlatGradientTail:
         if self.fused is not None:
             self.fused.reset()
         self.flat.zero_grad()
+        if self.monitor is not None:                         # the warm-up's losses and updates are not the run's
+            self.monitor.reset()
 
     # -- the graphed half of a step's state_dict() / load_state_dict() (step_state.py; the eager half: step_state.EagerTail)
     def require_single_rank(self, what):
@@ -1193,7 +1262,7 @@ class GraphedTargetStep(StepState):
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
                  swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None,
-                 pad_rows: bool = False):
+                 pad_rows: bool = False, skip_nonfinite: bool = False):
         """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
@@ -1228,7 +1297,8 @@ class GraphedTargetStep(StepState):
         real rows (label -100 is its ignore_index).  Nothing captured depends on B other than through shapes the padding keeps fixed: the only
         cross-row operations are the head's BatchNorm and the filter's "any face passed" (both over the device frame count) and the loss's mean.
         Needs frame_capacity (compact frames change shape with the batch: ValueError) and the default single-graph mode on one rank
-        (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
+        (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
+        `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too; several capacities share the one monitor."""
         from . import ops
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
@@ -1269,8 +1339,9 @@ class GraphedTargetStep(StepState):
         flat = averager if averager is not None else GradientAverager(step_parameters(self.mm, masters), hooks=False)
         if flat._handles:
             raise ValueError("GraphedTargetStep needs GradientAverager(..., hooks=False): the exchange runs between the graphs")
+        self.monitor = TrainMonitor(dev) if skip_nonfinite else None
         self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.trg_accumulation_steps > 1, masters=masters, exchanging=bool(flat.active),
-                                            capture_tables=max(4, len(self.capacities or ())))
+                                            capture_tables=max(4, len(self.capacities or ())), monitor=self.monitor)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         self.mm.text_stream = None
         # inside ONE graph the fork / join below become parallel branches; which hardware queue the branches replay on is the
@@ -1497,6 +1568,7 @@ class GraphedTargetStep(StepState):
         got = torch.autograd.grad(loss, [feat_d, preds_d] + leaves, allow_unused=True)
         for l, gr in zip(leaves, got[2:]):
             l.grad = gr
+        self._monitor_loss(loss)
         return loss.detach(), new_mask, got[0], got[1]
 
     def _text_backward(self, feat, dfeat, handover=True):
@@ -1537,6 +1609,11 @@ class GraphedTargetStep(StepState):
             if self.sched is not None:
                 self.sched.step()
         return self.loss, self.new_mask
+
+    def _monitor_loss(self, loss):
+        """skip_nonfinite: one launch behind the micro-step's loss that counts it in the monitor (undivided: times trg_accumulation_steps)"""
+        if self.monitor is not None:
+            self.monitor.loss(loss.detach(), self.args.trg_accumulation_steps)
 
     def _swin_preds(self, frames, num_imgs):
         """Swin's target-task forward on the step's frames; with a frame capacity: packed on the device first (-> self.frame_counts)"""
@@ -1636,6 +1713,7 @@ class GraphedTargetStep(StepState):
         if whole:                                            # one piece: autograd runs the text branch's backward beside Swin's
             loss.backward()
             self.tail.hand_over()
+            self._monitor_loss(loss)
             return loss.detach(), new_mask, None
         # backward, first piece: every leaf the optimizer steps plus Swin's output (the autograd graph below `preds` -- Swin -- is
         # left untouched, with its saved activations, for the second piece)
@@ -1666,6 +1744,7 @@ class GraphedTargetStep(StepState):
         #  tried: the ~870 gradient tensors then stay allocated across the graph and the step got 2.8 ms SLOWER; not kept.)
         # N > 1 (two-piece backward): the same one-pass hand-over in front of the exchange; its norm is of the LOCAL gradients and is discarded
         self.tail.hand_over()
+        self._monitor_loss(loss)
         return loss.detach(), new_mask, (x_cut, dpreds)
 
     # two-piece backward: cut behind Swin stage SWIN_CUT.  Measured at one rank with the exchange forced (ms per step, same call; the
@@ -1843,11 +1922,13 @@ class GraphedAuxStep(StepState):
     model) as two HIP graphs, same construction as GraphedTargetStep; the Swin gradients are the exchanged ones here."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "aux", ("swin",), "aux_accumulation_steps"
 
-    def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False):
+    def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False,
+                 skip_nonfinite: bool = False):
         """`pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
         pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
         device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
-        (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
+        (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
+        `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too."""
         from . import ops
         from .parallel import GradientAverager
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
@@ -1858,7 +1939,8 @@ class GraphedAuxStep(StepState):
         self.i_batch = 0
         dev = images.device
         flat = averager if averager is not None else GradientAverager(self.swin.parameters(), hooks=False)
-        self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.aux_accumulation_steps > 1, exchanging=bool(flat.active))
+        self.monitor = TrainMonitor(dev) if skip_nonfinite else None
+        self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.aux_accumulation_steps > 1, exchanging=bool(flat.active), monitor=self.monitor)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.swin.parameters()) + list(self.swin.buffers())]
         cap = distinct_stream(dev)
@@ -1887,6 +1969,8 @@ class GraphedAuxStep(StepState):
             loss = self.swin(images, False, labels, F.cross_entropy) / self.args.aux_accumulation_steps
         loss.backward()
         self.tail.hand_over()
+        if self.monitor is not None:
+            self.monitor.loss(loss.detach(), self.args.aux_accumulation_steps)
         return loss.detach()
 
     def __call__(self, images, labels):
@@ -1974,10 +2058,12 @@ class GraphedUnimodalStep(StepState):
     `pad_rows=True` is the way: the capture runs forward_loss(..., valid_mean=True) -- the loss is the mean over the rows that have a label, the
     same bits as the plain loss on a full batch --, and a batch with 1 <= b <= B rows is padded to B by pad_unimodal_batch (copies of row 0, label
     -100) and replayed through the same graphs, flat buffers and optimizer state; the loss returned is the mean over the b real rows /
-    trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded."""
+    trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
+    `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = UnimodalStep.STATE_KIND, UnimodalStep.STATE_MODELS, UnimodalStep.STATE_WINDOW
 
-    def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False):
+    def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False,
+                 skip_nonfinite: bool = False):
         from . import ops
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
         self.autocast_dtype = autocast_dtype
@@ -1988,7 +2074,8 @@ class GraphedUnimodalStep(StepState):
         self.i_batch = 0
         dev = feature.device
         # this step never exchanges (exchanging=False): the hand-over's norm is always the update's
-        self.tail = tail = FlatGradientTail(self.model.parameters(), optimizer, args.clip, args.trg_accumulation_steps > 1)
+        self.monitor = TrainMonitor(dev) if skip_nonfinite else None
+        self.tail = tail = FlatGradientTail(self.model.parameters(), optimizer, args.clip, args.trg_accumulation_steps > 1, monitor=self.monitor)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.model.parameters()) + list(self.model.buffers())]
         cap = distinct_stream(dev)
@@ -2021,6 +2108,8 @@ class GraphedUnimodalStep(StepState):
         loss = loss / self.args.trg_accumulation_steps
         loss.backward()
         self.tail.hand_over()
+        if self.monitor is not None:
+            self.monitor.loss(loss.detach(), self.args.trg_accumulation_steps)
         return loss.detach()
 
     def __call__(self, batch):

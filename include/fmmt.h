@@ -520,6 +520,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_eval_collect.h"
 /* The pooling head's loss as a mean over the rows that have a label (fmmt_pool_head_fwd_rows / _bwd_rows: a short last batch padded to a captured shape): likewise, held to _lib.POOL_HEAD_ROWS_SIGNATURES. */
 #include "fmmt_pool_head_rows.h"
+/* The update that is skipped when the gradient norm is not finite, and the run's counters on the device (fmmt_adamw_batch_guarded, fmmt_guard_commit, fmmt_monitor_loss): likewise, held to _lib.GUARD_SIGNATURES. */
+#include "fmmt_guard.h"
 
 #ifdef __cplusplus
 }
