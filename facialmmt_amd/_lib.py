@@ -126,6 +126,13 @@ GUARD_SIGNATURES = {
 # the layout of `words` (include/fmmt_guard.h FMMT_GUARD_*): the one place Python states it; train_step.TrainMonitor reads through these
 GUARD_LOSS_SUM, GUARD_MICRO_STEPS, GUARD_NONFINITE_LOSSES, GUARD_APPLIED, GUARD_SKIPPED, GUARD_LAST_NORM, GUARD_WORDS = 0, 1, 2, 3, 4, 5, 6
 
+# include/fmmt_digest.h, one to one: a seventh table and header for the same reason -- the replica digest over fmmt_adamw_batch's descriptor
+# table (tests/test_digest_cpu.py::test_digest_header_signatures_and_library_agree holds table, header and library together)
+DIGEST_SIGNATURES = {
+    "fmmt_param_digest": (_i, [_i, _i, _p, _p, _p, _p]),
+}
+DIGEST_WORDS = 6          # (S1, S2) of the parameters, the first moments, the second moments
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -146,7 +153,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

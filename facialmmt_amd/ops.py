@@ -378,6 +378,24 @@ def monitor_loss(loss, scale, words):
     check(_lib.load().fmmt_monitor_loss(_p(loss), float(scale), _guard_words(words), _st()), "fmmt_monitor_loss")
 
 
+def param_digest(n, blocks, desc, out=None, partial=None):
+    """fmmt_param_digest over adamw_batch's descriptor table (`n` records, `blocks` blocks of 4096 elements): six int64 words on the device --
+    (S1, S2) of the parameters, of the first and of the second moments, S1 = sum of the elements' 32 bits, S2 = that sum weighted with
+    (element index + 1) + (record index + 1) * 2^32, both mod 2^64 (include/fmmt_digest.h).  The words are uint64 bit patterns in an int64
+    tensor (compare them, or view them as uint64 on the host).  `out`: a contiguous int64 tensor of six entries to write into; `partial`:
+    6 * blocks int64 words of scratch (default: allocated per call).  Asynchronous on the current stream."""
+    if out is None:
+        out = torch.empty(6, dtype=torch.int64, device=desc.device)
+    elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != 6:
+        raise ValueError("param_digest: out is a contiguous int64 tensor of six entries")
+    if partial is None:
+        partial = torch.empty(6 * max(int(blocks), 1), dtype=torch.int64, device=desc.device)
+    elif partial.dtype != torch.int64 or not partial.is_contiguous() or partial.numel() < 6 * blocks:
+        raise ValueError("param_digest: partial is a contiguous int64 tensor of at least 6 * blocks entries")
+    check(_lib.load().fmmt_param_digest(n, blocks, _p(desc), _p(partial), _p(out), _st()), "fmmt_param_digest")
+    return out
+
+
 class VendorLinearFn(torch.autograd.Function):
     """y = x W^T + b with the vendor library's GEMMs (torch.nn.functional.linear / matmul) and fmmt_colsum for the bias gradient:
     the text encoder's Linear layers (few thousand tokens: hipBLASLt's ground; its autograd formula spends a memset and a

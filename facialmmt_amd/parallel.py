@@ -248,6 +248,33 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0, process_group=No
             dist.broadcast(t, src, group=process_group)
 
 
+def replicas_agree(digest, process_group=None):
+    """Do all ranks hold the same parameter and moment bits?  `digest`: this rank's six int64 words (a graphed step's replica_digest(),
+    FusedClipAdamW.digest()).  One all_gather of the six words; returns the list of every rank's digest (host int64 tensors, rank order) when
+    they are all equal, raises RuntimeError naming the first rank and word that differ from rank 0's otherwise -- on every rank, since every
+    rank sees the same gathered words.  World size 1 (or no process group): [digest] on the host, without a collective."""
+    names = ("parameters S1", "parameters S2", "first moments S1", "first moments S2", "second moments S1", "second moments S2")
+    if digest.dtype != torch.int64 or digest.numel() != len(names):
+        raise ValueError("replicas_agree: the six int64 words of a replica digest")
+    world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+    if world == 1:
+        return [digest.detach().cpu()]
+    mine = digest.detach().reshape(-1).contiguous()
+    if dist.get_backend(process_group) != "nccl":          # gloo gathers host tensors only; RCCL device tensors only
+        mine = mine.cpu()
+    elif not mine.is_cuda:
+        mine = mine.cuda()
+    got = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(got, mine, group=process_group)
+    got = [g.cpu() for g in got]
+    for r in range(1, world):
+        for w in range(len(names)):
+            if int(got[r][w]) != int(got[0][w]):
+                raise RuntimeError(f"replicas_agree: rank {r} differs from rank 0 in word {w} ({names[w]}): "
+                                   f"{int(got[r][w]) & 0xFFFFFFFFFFFFFFFF:#018x} against {int(got[0][w]) & 0xFFFFFFFFFFFFFFFF:#018x}")
+    return got
+
+
 def shard_utterances(n_global: int, rank: int, world: int):
     """contiguous split of a global batch of utterances across ranks"""
     per = (n_global + world - 1) // world

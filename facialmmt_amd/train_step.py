@@ -194,6 +194,32 @@ def pad_aux_batch(images, labels, rows):
     return _pad_const(images, extra), _pad_const(torch.as_tensor(labels), extra, IGNORE_LABEL)
 
 
+def row_weight(b, world, global_rows, captured_rows=None):
+    """The factor a rank multiplies its mean loss over `b` real rows with so that the all-reduce's mean over `world` ranks is the mean over the
+    `global_rows` real rows all ranks hold together: b * world / global_rows (sum_r (w_r / world) * mean_r = sum_r b_r mean_r / global_rows).
+    global_rows None -- every rank holds the same number of real rows, DistributedSampler's contract -- gives 1.0.  ValueError unless 1 <= b and
+    b + (world - 1) <= global_rows <= world * captured_rows (every other rank holds at least one and at most the captured number of rows;
+    `captured_rows` None: no upper bound is known).  Pure host code.  A rank without any real row is not covered: the padding refuses b == 0."""
+    b, world = int(b), int(world)
+    if b < 1 or world < 1:
+        raise ValueError(f"row_weight: a rank holds at least one real row and the world at least one rank, got b={b}, world={world}")
+    if global_rows is None:
+        return 1.0
+    g = int(global_rows)
+    if g < b + (world - 1) or (captured_rows is not None and g > world * int(captured_rows)):
+        raise ValueError(f"row_weight: global_rows={g} is impossible for a rank with {b} real rows among {world} ranks"
+                         + (f" of at most {int(captured_rows)} rows each" if captured_rows is not None else "")
+                         + f" ({b + world - 1} <= global_rows" + (f" <= {world * int(captured_rows)})" if captured_rows is not None else ")"))
+    return b * world / g
+
+
+def _check_global_rows(who, global_rows, weight_word, b, world, captured_rows):
+    """the graphed steps' __call__: the weight this micro-step's loss is differentiated with (row_weight), or ValueError -- before any copy or launch"""
+    if global_rows is not None and weight_word is None:
+        raise ValueError(f"{who}: global_rows needs pad_rows=True and an active gradient exchange (without them every rank's mean counts alike)")
+    return row_weight(b, world, global_rows, captured_rows)
+
+
 class _Branch(torch.nn.Module):
     """One branch of the multimodal forward as a module of its own, so that torch.cuda.make_graphed_callables sees
     exactly the parameters it uses.  Shares the owner's sub-modules (same Parameter objects); never registered on the
@@ -1055,6 +1081,16 @@ class FusedClipAdamW:
             arr[i] = r
         self.desc = torch.from_numpy(arr.view(np.uint8).copy()).to(dev)
         self.n, self.blocks = len(recs), blocks
+        self._digest_partial = None
+
+    def digest(self, out=None):
+        """the replica digest of what this object steps (ops.param_digest on its own descriptor table): six int64 words on the device -- (S1, S2)
+        of the parameters, the first and the second moments -- that are equal on two ranks exactly when (up to a 2^-64 coincidence) the bits are;
+        two launches, no host synchronisation; the scratch for the per-block words is allocated on the first call and kept"""
+        from . import ops
+        if self._digest_partial is None:
+            self._digest_partial = torch.empty(6 * self.blocks, dtype=torch.int64, device=self.desc.device)
+        return ops.param_digest(self.n, self.blocks, self.desc, out=out, partial=self._digest_partial)
 
     def reset(self):
         self.step.zero_()
@@ -1188,6 +1224,14 @@ class FlatGradientTail:
         for l, _ in self.pairs:                              # the next backward must produce fresh gradient tensors
             l.grad = None
 
+    def replica_digest(self):
+        """FusedClipAdamW.digest() of the parameters and moments this tail steps (compare across ranks: parallel.replicas_agree); only with the
+        fused update, which owns the descriptor table -- ValueError otherwise, as skip_nonfinite"""
+        if self.fused is None:
+            raise ValueError("replica_digest needs the fused update (FusedClipAdamW.eligible: one group of torch.optim.AdamW / HFAdamW with a device "
+                             "learning rate over fp32 device parameters): the digest runs over its descriptor table")
+        return self.fused.digest()
+
     def undo_warmup(self):
         """what the warm-up passes in front of a capture left in the optimizer and the flat buffers (graph_capture.warmup_undone calls it)"""
         _reset_optimizer_state(self.opt)
@@ -1280,14 +1324,16 @@ class GraphedTargetStep(StepState):
         loader pads them, (B, Lv, ...), with num_imgs the real counts; the capture holds ops.pack_frames (real frames to the front of F_cap rows,
         the count in a device word) -> Swin on all F_cap rows with the head's BatchNorm over the real ones -> the frame filter with the same count.
         num_imgs as a list or CPU tensor (the reference's collate) is checked against F_cap on the host (ValueError); a device tensor is the
-        caller's contract and `frame_counts` (int32 [n_valid, total], device) is there for a check at the end of an epoch.  Default single-graph
-        mode only: NotImplementedError together with pipeline_swin / branch_graphs / fork_streams / an active averager.
+        caller's contract and `frame_counts` (int32 [n_valid, total], device) is there for a check at the end of an epoch.  The default
+        single-graph mode and the two-piece mode of an active averager: NotImplementedError together with pipeline_swin / branch_graphs /
+        fork_streams.
         An ascending tuple (c_1 < ... < c_k) ("buckets", `frame_buckets`) captures the forward/backward graph once per capacity -- pack into c_i rows,
         Swin on c_i rows, everything behind it as above -- and a call replays the smallest that holds its batch (`frame_bucket`: num_imgs on the
         host; more frames than c_k: ValueError before any copy or launch; a device tensor replays c_k unread).  The captures share the static
         inputs, the flat gradient buffers with the hand-over's destinations, graph B, the optimizer state and learning-rate word, the bf16
         shadows, the generator and `frame_counts`, so an accumulation window may mix capacities; each keeps its saved activations in a memory pool
-        of its own (BUCKET_NOTE).  A capacity below the sample batch's total is warmed up and captured on the sample's counts cut down to fit, and
+        of its own (BUCKET_NOTE).  Under an active averager each capacity is a PAIR of graphs (A1_c, A2_c) in one pool, the exchange is issued
+        between them from the host and only sees the flat buffers: ranks may replay different capacities in the same step.  A capacity below the sample batch's total is warmed up and captured on the sample's counts cut down to fit, and
         every warm-up is undone as the single one is.  `capacities`: the tuple; `capacity`: the last call's; `replays`: {capacity: calls};
         `capture_bytes` / `capture_reserved_bytes`: {capacity: growth of torch.cuda.memory_allocated / memory_reserved over its capture} (the
         saved activations are free blocks of the capture's private pool once it ends: the reserved figure is the memory a capacity costs).
@@ -1296,8 +1342,9 @@ class GraphedTargetStep(StepState):
         same generator; the bucket is chosen from the padded num_imgs, which sum to the real frames; the loss is F.cross_entropy's mean over the
         real rows (label -100 is its ignore_index).  Nothing captured depends on B other than through shapes the padding keeps fixed: the only
         cross-row operations are the head's BatchNorm and the filter's "any face passed" (both over the device frame count) and the loss's mean.
-        Needs frame_capacity (compact frames change shape with the batch: ValueError) and the default single-graph mode on one rank
-        (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
+        Needs frame_capacity (compact frames change shape with the batch: ValueError); not with pipeline_swin / branch_graphs / fork_streams
+        (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.  Under an active
+        averager ranks may hold different numbers of real rows: pass `global_rows` to the call (ROW_WEIGHT_NOTE).
         `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too; several capacities share the one monitor."""
         from . import ops
         from .parallel import GradientAverager
@@ -1310,18 +1357,22 @@ class GraphedTargetStep(StepState):
         self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
         if self.pad_rows and frame_capacity is None:
             raise ValueError("pad_rows: only with frame_capacity (compact frames change their shape with the batch's rows)")
-        if self.pad_rows and (pipeline_swin or branch_graphs or fork_streams or bool(getattr(averager, "active", False))):
-            raise NotImplementedError("pad_rows: the default single-graph mode on one rank (not with pipeline_swin / branch_graphs / fork_streams / "
-                                      "an active gradient exchange)")
+        if self.pad_rows and (pipeline_swin or branch_graphs or fork_streams):
+            raise NotImplementedError("pad_rows: the default single-graph mode, or the two-piece mode of an active gradient exchange (not with "
+                                      "pipeline_swin / branch_graphs / fork_streams)")
+        if (self.pad_rows or frame_capacity is not None) and bool(getattr(averager, "active", False)) and not isinstance(averager, GradientAverager):
+            # the per-capacity pairs and the row weight are built on GradientAverager: its flat buffers are what the capacities share, its
+            # world size is what weights the rows.  Another object that calls itself active is an exchange this step has no path for.
+            raise NotImplementedError("pad_rows / frame_capacity under a gradient exchange: only with a parallel.GradientAverager(hooks=False)")
         self.capacities = frame_buckets(frame_capacity)    # None, (F_cap,) or the ascending buckets: ValueError before anything touches the GPU
         self.frame_capacity = None if self.capacities is None else self.capacities[-1]
         self.frame_counts = None
         self.capacity, self.replays, self.capture_bytes, self.capture_reserved_bytes = None, {c: 0 for c in self.capacities or ()}, {}, {}
         self._cap = self.frame_capacity                     # the capacity the pass in progress (warm-up, capture) packs into
         if self.frame_capacity is not None:
-            if self.pipeline or self.branches or self.forked or bool(getattr(averager, "active", False)):
-                raise NotImplementedError("frame_capacity: the default single-graph mode on one rank (not with pipeline_swin / branch_graphs / "
-                                          "fork_streams / an active gradient exchange)")
+            if self.pipeline or self.branches or self.forked:
+                raise NotImplementedError("frame_capacity: the default single-graph mode, or the two-piece mode of an active gradient exchange (not "
+                                          "with pipeline_swin / branch_graphs / fork_streams)")
             if batch[8].dim() < 3:
                 raise ValueError("frame_capacity: a positive number of frames, and `frames` as the loader pads them, (B, Lv, ...)")
             check_frame_total(batch[9], batch[8].shape[1], self.frame_capacity)
@@ -1340,6 +1391,11 @@ class GraphedTargetStep(StepState):
         if flat._handles:
             raise ValueError("GraphedTargetStep needs GradientAverager(..., hooks=False): the exchange runs between the graphs")
         self.monitor = TrainMonitor(dev) if skip_nonfinite else None
+        # ROW_WEIGHT_NOTE.  Padded rows under an exchange: the all-reduce takes the mean of the ranks' means, which is the mean over the real rows
+        # only when every rank holds as many.  One static fp32 word multiplies the loss that is DIFFERENTIATED (row_weight: b * world /
+        # global_rows, filled per call; 1.0 without global_rows); the loss returned and the one the monitor counts stay the rank's own mean.
+        # Captures without (pad_rows and an active exchange) have no such word and keep their launch sequence.
+        self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and flat.active) else None
         self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.trg_accumulation_steps > 1, masters=masters, exchanging=bool(flat.active),
                                             capture_tables=max(4, len(self.capacities or ())), monitor=self.monitor)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
@@ -1393,6 +1449,7 @@ class GraphedTargetStep(StepState):
         self.graph_a, self.graph_a2, self.graph_b = torch.cuda.CUDAGraph(), (torch.cuda.CUDAGraph() if self.split else None), torch.cuda.CUDAGraph()
         self.sets, self.side_stream, self.cur, self.prefetched = [], None, 0, None
         self._graphs = {}                                   # several capacities: capacity -> (graph A, its loss, its kept-frame mask)
+        self._graphs_a2 = {}                                # ... under an exchange: capacity -> graph A2 (graph A above is A1)
         if self.pipeline:
             # two sets (graph S: Swin forward; graph A': everything else), each in a memory pool of ITS OWN: S of one set replays beside A' of the
             # other, and inside a shared pool the capture of the second set would reuse blocks the first set's backward freed
@@ -1447,11 +1504,33 @@ class GraphedTargetStep(StepState):
         else:
           with capture_window(), ops.pinned_scope(self.shadows):
             if self.split:
-                with torch.cuda.graph(self.graph_a, stream=cap):
-                    self.loss, self.new_mask, swin_out = self._fwd_bwd_multimodal()
-                with torch.cuda.graph(self.graph_a2, pool=self.graph_a.pool(), stream=cap):
-                    self._bwd_swin(swin_out)
-                del swin_out
+                # One pair (A1_c, A2_c) per capacity c (a compact step or frame_capacity=int: the one pair), A2_c in A1_c's pool -- it continues from
+                # the activations A1_c saved -- and every pair in a pool of its own: BUCKET_NOTE below, unchanged.  The exchange between the two
+                # only sees the flat buffers, which no capacity sizes: ranks may replay different capacities in the same step.
+                for c in self.capacities or (None,):
+                    if multi:
+                        self._use_capacity(c, batch)
+                    own = not multi or c == self.capacities[-1]
+                    g1, g2 = (self.graph_a, self.graph_a2) if own else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
+                    before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
+                    with torch.cuda.graph(g1, stream=cap):
+                        loss, new_mask, swin_out = self._fwd_bwd_multimodal()
+                    with torch.cuda.graph(g2, pool=g1.pool(), stream=cap):
+                        self._bwd_swin(swin_out)
+                    del swin_out
+                    if c is not None:
+                        self.capture_bytes[c] = torch.cuda.memory_allocated(dev) - before[0]
+                        self.capture_reserved_bytes[c] = torch.cuda.memory_reserved(dev) - before[1]
+                    if multi:
+                        self._graphs[c], self._graphs_a2[c] = (g1, loss, new_mask), g2
+                        _KEEP_GRAPHS.append((g1, g2))
+                        # as on the single-graph bucket path: no Swin gradient survives into the next pair's capture -- here that includes the
+                        # parameters above the cut, whose .grad A1 assigns (`late` in _fwd_bwd_multimodal)
+                        self.swin.zero_grad(set_to_none=True)
+                self.loss, self.new_mask = loss, new_mask
+                if multi:
+                    with torch.cuda.graph(self.graph_b, stream=cap):
+                        tail.update()
             elif multi:
                 # BUCKET_NOTE.  One graph A per capacity, each in a memory pool of ITS OWN: a graph keeps its saved activations in its pool between
                 # its forward and its backward, and graphs that replay in an order the batches decide must not hand each other's blocks out.
@@ -1710,11 +1789,14 @@ class GraphedTargetStep(StepState):
                     t.record_stream(main)
             logits = mm.fusion_branch(pending[0], pending[1], audio, audio_mask, vis_concat, new_mask)
         loss = F.cross_entropy(logits.float(), labels) / args.trg_accumulation_steps
+        returned, w = loss, self.row_weight
+        if w is not None:                                    # ROW_WEIGHT_NOTE: the gradients carry the weight, the loss handed back does not
+            loss = loss * w
         if whole:                                            # one piece: autograd runs the text branch's backward beside Swin's
             loss.backward()
             self.tail.hand_over()
-            self._monitor_loss(loss)
-            return loss.detach(), new_mask, None
+            self._monitor_loss(returned)
+            return returned.detach(), new_mask, None
         # backward, first piece: every leaf the optimizer steps plus Swin's output (the autograd graph below `preds` -- Swin -- is
         # left untouched, with its saved activations, for the second piece)
         leaves = [l for l, _ in self.pairs if l.requires_grad]
@@ -1744,8 +1826,8 @@ class GraphedTargetStep(StepState):
         #  tried: the ~870 gradient tensors then stay allocated across the graph and the step got 2.8 ms SLOWER; not kept.)
         # N > 1 (two-piece backward): the same one-pass hand-over in front of the exchange; its norm is of the LOCAL gradients and is discarded
         self.tail.hand_over()
-        self._monitor_loss(loss)
-        return loss.detach(), new_mask, (x_cut, dpreds)
+        self._monitor_loss(returned)
+        return returned.detach(), new_mask, (x_cut, dpreds)
 
     # two-piece backward: cut behind Swin stage SWIN_CUT.  Measured at one rank with the exchange forced (ms per step, same call; the
     # single graph: 66.9): cut at Swin's output 71.6, behind stage 2: 72.3, stage 1: 70.9-71.0, stage 0: 69.7-69.9 -- the second piece
@@ -1797,29 +1879,36 @@ class GraphedTargetStep(StepState):
         self.loss, self.new_mask = st.loss, st.mask
         return st.loss, st.mask
 
-    def __call__(self, batch, next_batch=None):
+    def __call__(self, batch, next_batch=None, global_rows=None):
         """`next_batch` (pipeline_swin only): the batch the NEXT call will be given -- its Swin forward is replayed now, beside this step.  Pass
-        None in front of an auxiliary step (it moves Swin's weights: the prefetch would be thrown away) and for the last step of an epoch."""
+        None in front of an auxiliary step (it moves Swin's weights: the prefetch would be thrown away) and for the last step of an epoch.
+        `global_rows` (pad_rows under an active exchange only, ValueError otherwise): the real rows ALL ranks hold in this micro-step, which the
+        caller knows from its sampler -- the gradients are then those of the mean over these rows (ROW_WEIGHT_NOTE, row_weight; an impossible
+        value: ValueError before any copy or launch).  None: every rank holds the same number of real rows (DistributedSampler's contract).
+        Under an exchange with several capacities every rank picks its own bucket from its own host counts; `replays`, `capacity`,
+        `frame_counts`, `rows` and `padded_calls` are this rank's.  Not covered: a rank with no real row at all (b == 0 is refused)."""
         if len(batch) != len(self.static):
             raise ValueError(f"GraphedTargetStep: batch of {len(batch)} entries, captured with {len(self.static)}")
+        if global_rows is not None and (self.pipeline or self.branches):
+            raise ValueError("GraphedTargetStep: global_rows needs pad_rows=True and an active gradient exchange")
         if self.pipeline:
             return self._call_pipelined(batch, next_batch)
         if self.branches:
             return self._call_branches(batch)
         rows = self.static[7].shape[0]
-        if self.pad_rows:
-            b = len(batch[7])
-            if b != rows:
-                batch = pad_target_batch(batch, rows)       # ValueError for b == 0 or b > rows, before any copy or launch
-        else:
-            b = rows
-        graph_a = self.graph_a
+        b = len(batch[7]) if self.pad_rows else rows
+        weight = _check_global_rows("GraphedTargetStep", global_rows, self.row_weight, b, self.flat.world, rows)     # ValueError first of all
+        if self.pad_rows and b != rows:
+            batch = pad_target_batch(batch, rows)           # ValueError for b == 0 or b > rows, before any copy or launch
+        graph_a, graph_a2 = self.graph_a, self.graph_a2
         if self.capacities is not None:
             # the smallest capacity that holds the batch (host counts; a device tensor: the largest, unread); ValueError before any copy or launch
             c = frame_bucket(batch[9], self.static[8].shape[1], self.capacities)
             if self._graphs:
-                graph_a = self._graphs[c][0]
+                graph_a, graph_a2 = self._graphs[c][0], self._graphs_a2.get(c)
         copy_into_static(self.static, batch, "GraphedTargetStep")
+        if self.row_weight is not None:
+            self.row_weight.fill_(weight)                   # a device fill: no host synchronisation
         graph_a.replay()
         self.rows = b
         self.padded_calls += int(b != rows)
@@ -1834,8 +1923,8 @@ class GraphedTargetStep(StepState):
             self.flat.exchange_begin()                     # no-op at world size 1; the collectives run beside graph A2
             if self.timing is not None:
                 self.timing["begin"].record()
-        if self.graph_a2 is not None:
-            self.graph_a2.replay()
+        if graph_a2 is not None:
+            graph_a2.replay()
         if last:
             if self.timing is not None:
                 self.timing["a2_done"].record()
@@ -1847,6 +1936,11 @@ class GraphedTargetStep(StepState):
             if self.sched is not None:
                 self.sched.step()
         return self.loss, self.new_mask
+
+    def replica_digest(self):
+        """six int64 device words over the bits of every stepped parameter and its moments (FlatGradientTail.replica_digest; compare across
+        ranks with parallel.replicas_agree); ValueError without the fused update"""
+        return self.tail.replica_digest()
 
     def time_exchange(self, on: bool = True):
         """record three events per step around the exchange (issue / Swin backward enqueued / collectives waited for):
@@ -1928,6 +2022,8 @@ class GraphedAuxStep(StepState):
         pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
         device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
         (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
+        Under an active averager `__call__(images, labels, global_rows=...)` weights the differentiated loss with row_weight (ROW_WEIGHT_NOTE at
+        GraphedTargetStep): ranks that hold different numbers of real rows then step on the mean over all real rows.
         `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too."""
         from . import ops
         from .parallel import GradientAverager
@@ -1939,6 +2035,7 @@ class GraphedAuxStep(StepState):
         self.i_batch = 0
         dev = images.device
         flat = averager if averager is not None else GradientAverager(self.swin.parameters(), hooks=False)
+        self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and flat.active) else None
         self.monitor = TrainMonitor(dev) if skip_nonfinite else None
         self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.aux_accumulation_steps > 1, exchanging=bool(flat.active), monitor=self.monitor)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
@@ -1967,18 +2064,24 @@ class GraphedAuxStep(StepState):
             loss = self.swin(images, False, labels, F.cross_entropy, n_valid=self.n_valid) / self.args.aux_accumulation_steps
         else:
             loss = self.swin(images, False, labels, F.cross_entropy) / self.args.aux_accumulation_steps
-        loss.backward()
+        (loss if self.row_weight is None else loss * self.row_weight).backward()
         self.tail.hand_over()
         if self.monitor is not None:
             self.monitor.loss(loss.detach(), self.args.aux_accumulation_steps)
         return loss.detach()
 
-    def __call__(self, images, labels):
+    def __call__(self, images, labels, global_rows=None):
+        """`global_rows`: GraphedTargetStep.__call__'s -- the real rows all ranks hold in this micro-step; pad_rows under an active exchange only"""
         rows = b = self.static[0].shape[0]
-        if self.pad_rows and images.dim() == self.static[0].dim() and images.shape[0] != rows:
+        padding = self.pad_rows and images.dim() == self.static[0].dim() and images.shape[0] != rows
+        if padding:
             b = images.shape[0]
+        weight = _check_global_rows("GraphedAuxStep", global_rows, self.row_weight, b, self.flat.world, rows)     # ValueError first of all
+        if padding:
             images, labels = pad_aux_batch(images, labels, rows)     # ValueError for b == 0 or b > rows, before any copy or launch
         copy_into_static(self.static, (images, labels), "GraphedAuxStep")
+        if self.row_weight is not None:
+            self.row_weight.fill_(weight)
         if self.n_valid is not None:
             self.n_valid.fill_(b)                            # a device fill: no host synchronisation
         self.graph_a.replay()
@@ -1986,6 +2089,10 @@ class GraphedAuxStep(StepState):
         self.padded_calls += int(b != rows)
         replay_update(self, self.args.aux_accumulation_steps, self.flat.exchange_all)     # Swin's gradients: 187 MB fp32, nothing left in the step to hide them behind
         return self.loss
+
+    def replica_digest(self):
+        """GraphedTargetStep.replica_digest's, over Swin's parameters and moments"""
+        return self.tail.replica_digest()
 
     def start_epoch(self):
         """a partial accumulation window does not carry into the next epoch (train.py:17,20 restart per epoch)"""
@@ -2059,11 +2166,14 @@ class GraphedUnimodalStep(StepState):
     same bits as the plain loss on a full batch --, and a batch with 1 <= b <= B rows is padded to B by pad_unimodal_batch (copies of row 0, label
     -100) and replayed through the same graphs, flat buffers and optimizer state; the loss returned is the mean over the b real rows /
     trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
-    `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too."""
+    `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too.
+    `averager` (default None: this step never exchanges): a GradientAverager(hooks=False) over the model's parameters -- its buckets are averaged
+    over the ranks between graph A and graph B of a window's last micro-step, as GraphedAuxStep does it; with pad_rows the call then takes
+    `global_rows` (ROW_WEIGHT_NOTE at GraphedTargetStep)."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = UnimodalStep.STATE_KIND, UnimodalStep.STATE_MODELS, UnimodalStep.STATE_WINDOW
 
     def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, averager=None):
         from . import ops
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
         self.autocast_dtype = autocast_dtype
@@ -2073,9 +2183,14 @@ class GraphedUnimodalStep(StepState):
         self.shadows = None
         self.i_batch = 0
         dev = feature.device
-        # this step never exchanges (exchanging=False): the hand-over's norm is always the update's
+        # without an averager this step never exchanges (exchanging=False): the hand-over's norm is then always the update's
+        if averager is not None and averager._handles:
+            raise ValueError("GraphedUnimodalStep needs GradientAverager(..., hooks=False): the exchange runs between the graphs")
+        self.exchange = averager.exchange_all if averager is not None else None
+        self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and averager is not None and averager.active) else None
         self.monitor = TrainMonitor(dev) if skip_nonfinite else None
-        self.tail = tail = FlatGradientTail(self.model.parameters(), optimizer, args.clip, args.trg_accumulation_steps > 1, monitor=self.monitor)
+        self.tail = tail = FlatGradientTail(averager if averager is not None else self.model.parameters(), optimizer, args.clip,
+                                            args.trg_accumulation_steps > 1, exchanging=bool(averager is not None and averager.active), monitor=self.monitor)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.model.parameters()) + list(self.model.buffers())]
         cap = distinct_stream(dev)
@@ -2106,24 +2221,34 @@ class GraphedUnimodalStep(StepState):
             loss, logits = self.model.forward_loss(feature, mask, labels, **kw)
         self.logits = logits.detach()
         loss = loss / self.args.trg_accumulation_steps
-        loss.backward()
+        (loss if self.row_weight is None else loss * self.row_weight).backward()
         self.tail.hand_over()
         if self.monitor is not None:
             self.monitor.loss(loss.detach(), self.args.trg_accumulation_steps)
         return loss.detach()
 
-    def __call__(self, batch):
+    def __call__(self, batch, global_rows=None):
+        """`global_rows`: GraphedTargetStep.__call__'s -- the real rows all ranks hold in this micro-step; pad_rows under an active exchange only"""
         feature, mask, labels = batch
         rows = b = self.static[0].shape[0]
-        if self.pad_rows and feature.dim() == self.static[0].dim() and feature.shape[0] != rows:
+        padding = self.pad_rows and feature.dim() == self.static[0].dim() and feature.shape[0] != rows
+        if padding:
             b = feature.shape[0]
+        weight = _check_global_rows("GraphedUnimodalStep", global_rows, self.row_weight, b, self.flat.world, rows)     # ValueError first of all
+        if padding:
             feature, mask, labels = pad_unimodal_batch(batch, rows)     # ValueError for b == 0 or b > rows, before any copy or launch
         copy_into_static(self.static, (feature, mask, labels), "GraphedUnimodalStep")
+        if self.row_weight is not None:
+            self.row_weight.fill_(weight)
         self.graph_a.replay()
         self.rows = b
         self.padded_calls += int(b != rows)
-        replay_update(self, self.args.trg_accumulation_steps)
+        replay_update(self, self.args.trg_accumulation_steps, self.exchange)
         return self.loss
+
+    def replica_digest(self):
+        """GraphedTargetStep.replica_digest's, over the model's parameters and moments"""
+        return self.tail.replica_digest()
 
     def start_epoch(self):
         """a partial accumulation window does not carry into the next epoch (train.py:250-251 restart per epoch)"""

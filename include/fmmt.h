@@ -522,6 +522,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_pool_head_rows.h"
 /* The update that is skipped when the gradient norm is not finite, and the run's counters on the device (fmmt_adamw_batch_guarded, fmmt_guard_commit, fmmt_monitor_loss): likewise, held to _lib.GUARD_SIGNATURES. */
 #include "fmmt_guard.h"
+/* The replica digest over the optimizer's descriptor table (fmmt_param_digest): likewise, held to _lib.DIGEST_SIGNATURES. */
+#include "fmmt_digest.h"
 
 #ifdef __cplusplus
 }
