@@ -133,6 +133,13 @@ DIGEST_SIGNATURES = {
 }
 DIGEST_WORDS = 6          # (S1, S2) of the parameters, the first moments, the second moments
 
+# include/fmmt_eval_shard.h, one to one: an eighth table and header for the same reason -- the collecting metric update with a device-held row count
+# and the merge of the ranks' shards (tests/test_eval_shard_cpu.py::test_eval_shard_header_signatures_and_library_agree holds table, header and library together)
+EVAL_SHARD_SIGNATURES = {
+    "fmmt_eval_accumulate_rows": (_i, [_i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int64, _p]),
+    "fmmt_eval_merge": (_i, [_i, _i, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p, _p]),
+}
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -153,7 +160,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,8 @@
 //   in LDS, whatever B is, so the sum is deterministic; the counts go through integer LDS atomics (order-free) and leave with ordinary stores.
 // fmmt_eval_accumulate_at (include/fmmt_eval_collect.h): the same update, the rows of the batch also kept -- logits, label, argmax -- at a row index
 //   read from a device word that the kernel then advances, so that a captured graph collects a whole split; same body, same accumulator bits.
+// fmmt_eval_accumulate_rows (include/fmmt_eval_shard.h): that update with the number of rows that exist in a second device word -- a short batch
+//   padded to the captured B stores and counts its real rows only and advances the cursor by them; the same body once more.
 #include "fmmt_common.h"
 #include "../../include/fmmt.h"
 
@@ -181,6 +183,22 @@ __global__ __launch_bounds__(EA_THREADS) void eval_accumulate_at_kernel(int B, i
     if (threadIdx.x == 0) *cursor = base + B;                // also when rows were dropped: cursor > out_capacity reports the overflow
 }
 
+// The collecting update with the batch's REAL row count in a device word as well: a short batch padded to the captured B.  The body is instantiated
+// with b = clamp(*n_rows, 0, B) in the place of B, so a row at or behind b is not read, stored or counted whatever its label says, and b == B is
+// eval_accumulate_at_kernel instruction for instruction behind the two loads.  Both words are read by every thread in front of the barrier.
+template <typename T>
+__global__ __launch_bounds__(EA_THREADS) void eval_accumulate_rows_kernel(int B, int NL, const T* __restrict__ logits, int ld, const long long* __restrict__ labels,
+                                                                          double* __restrict__ loss_sum, long long* __restrict__ count,
+                                                                          long long* __restrict__ confusion, long long* cursor, const int* __restrict__ n_rows,
+                                                                          float* __restrict__ logits_out, long long* __restrict__ labels_out,
+                                                                          int* __restrict__ pred_out, long long out_capacity) {
+    const long long base = *cursor;
+    const int b = min(max(*n_rows, 0), B);
+    __syncthreads();                                         // every thread holds the old cursor before anything below may write the new one
+    eval_accumulate_body<T>(b, NL, logits, ld, labels, loss_sum, count, confusion, nullptr, logits_out, labels_out, pred_out, base, out_capacity);
+    if (threadIdx.x == 0) *cursor = base + b;
+}
+
 }  // namespace
 
 extern "C" int fmmt_emotion_head_fwd(int dtype, int N, int K, int H, int NL, const void* feats, int ld, const float* w1, const float* b1, const float* w2,
@@ -231,6 +249,27 @@ extern "C" int fmmt_eval_accumulate_at(int dtype, int B, int NL, const void* log
     else
         hipLaunchKernelGGL(eval_accumulate_at_kernel<float>, dim3(1), dim3(EA_THREADS), 0, st, B, NL, (const float*)logits, ld, (const long long*)labels, loss_sum,
                            (long long*)count, (long long*)confusion, (long long*)cursor, logits_out, (long long*)labels_out, pred_out, (long long)out_capacity);
+    FMMT_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fmmt_eval_accumulate_rows(int dtype, int B, int NL, const void* logits, int ld, const int64_t* labels, double* loss_sum, int64_t* count,
+                                         int64_t* confusion, int64_t* cursor, const int32_t* n_rows, float* logits_out, int64_t* labels_out,
+                                         int32_t* pred_out, int64_t out_capacity, void* stream) {
+    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
+    if (B <= 0 || B > EA_THREADS || NL <= 0 || NL > EH_MAXNL || ld < NL || out_capacity < 0) return FMMT_EINVAL;
+    if (!logits || !labels || !loss_sum || !count || !confusion || !cursor || !n_rows || !logits_out || !labels_out) return FMMT_EINVAL;
+    if (((uintptr_t)loss_sum | (uintptr_t)count | (uintptr_t)confusion | (uintptr_t)labels | (uintptr_t)cursor | (uintptr_t)labels_out) & 7) return FMMT_EALIGN;
+    if ((uintptr_t)n_rows & 3) return FMMT_EALIGN;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == FMMT_BF16)
+        hipLaunchKernelGGL(eval_accumulate_rows_kernel<bf16>, dim3(1), dim3(EA_THREADS), 0, st, B, NL, (const bf16*)logits, ld, (const long long*)labels, loss_sum,
+                           (long long*)count, (long long*)confusion, (long long*)cursor, (const int*)n_rows, logits_out, (long long*)labels_out, pred_out,
+                           (long long)out_capacity);
+    else
+        hipLaunchKernelGGL(eval_accumulate_rows_kernel<float>, dim3(1), dim3(EA_THREADS), 0, st, B, NL, (const float*)logits, ld, (const long long*)labels, loss_sum,
+                           (long long*)count, (long long*)confusion, (long long*)cursor, (const int*)n_rows, logits_out, (long long*)labels_out, pred_out,
+                           (long long)out_capacity);
     FMMT_CHECK_LAUNCH();
     return 0;
 }

@@ -21,7 +21,14 @@ Departures from the reference, on purpose:
   * `gumbel="off"` (not the default) evaluates without the Gumbel noise: the reference keeps F.gumbel_softmax in evaluation too, so its score is a
     random variable of the generator state; "off" is the deterministic variant.  With `frame_capacity` the noise is drawn for every row of the
     capacity, so under "sample" the numbers a given seed hands to a given frame -- and with them the score -- also depend on the capacity, i.e.
-    on which bucket a batch was replayed in: one more way in which that score is a draw, not a constant.  "off" does not depend on the bucket."""
+    on which bucket a batch was replayed in: one more way in which that score is a draw, not a constant.  "off" does not depend on the bucket.
+    The same holds for a split SHARDED over ranks (`evaluate(sharded=True)`, parallel.eval_shard): every rank draws from its own generator, so the
+    sharded score under "sample" is another draw than the single-rank one; under "off" it does not depend on the number of ranks.
+
+A short last batch (MELD's validation and test splits both end short at 4 per batch, and of a sharded split the last non-empty rank always does):
+`GraphedEvalStep(pad_rows=True)` pads it to the captured rows (train_step.pad_target_batch) and replays it; a device word tells the collecting metric
+update how many rows exist (ops.eval_accumulate_rows).  Several ranks: each evaluates a contiguous block of whole batches, `MeldMetrics.gather_merge`
+all-gathers accumulators and rows and ops.eval_merge makes the one split of them on the device, in dataset order, the same on every rank."""
 from __future__ import annotations
 
 import contextlib
@@ -29,10 +36,11 @@ import types
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import ops
 from .graph_capture import _KEEP_GRAPHS, capture_window, check_static_shapes, copy_into_static, distinct_stream, require_packet_capture_off, warmup_undone
-from .train_step import _clamp_counts, _pin_shadows, check_frame_total, frame_buckets, fused_inference, pick_bucket, select_frames  # noqa: F401
+from .train_step import _clamp_counts, _pin_shadows, check_frame_total, frame_buckets, fused_inference, pad_target_batch, pick_bucket, select_frames  # noqa: F401
 
 EMOTIONS = ("Neutral", "Surprise", "Fear", "Sadness", "Joy", "Disgust", "Anger")      # class order of eval_meld (utils/eval_metrics.py:27)
 
@@ -79,7 +87,10 @@ class MeldMetrics:
     `collect_rows` (None: nothing below exists): the metrics also COLLECT the split -- `results` (collect_rows, num_labels) fp32, `truths`
     (collect_rows,) int64 and `cursor`, one int64 device word -- through ops.eval_accumulate_at: every update stores its rows at the cursor and
     advances it on the device, so the update inside a captured graph fills the buffers front to back.  Rows behind collect_rows are counted and
-    not kept; `collected()` then raises.  The cursor lives behind the accumulators in one allocation: one copy brings both to the host."""
+    not kept; `collected()` then raises.  The cursor lives behind the accumulators in one allocation: one copy brings both to the host.
+
+    `gather_merge()` (collecting metrics only) makes the whole split of the shards W ranks evaluated: `merged`, a MeldMetrics(collect_rows =
+    W * collect_rows) built on first use, whose result() / collected() are the split's; this object stays the rank's own."""
 
     def __init__(self, num_labels: int = 7, device="cuda", collect_rows=None):
         if not 1 <= num_labels <= 8:
@@ -96,16 +107,21 @@ class MeldMetrics:
         self.acc, self.cursor = self.words[:n], self.words[n:]
         self.results = torch.zeros(self.collect_rows, num_labels, dtype=torch.float32, device=device)
         self.truths = torch.zeros(self.collect_rows, dtype=torch.int64, device=device)
+        self.merged = None
 
     def reset(self):
         (self.acc if self.collect_rows is None else self.words).zero_()          # in place: a captured graph keeps writing to this tensor
 
-    def update(self, logits, labels, logits_out=None, out_offset=0, pred=False):
-        """logits (B, num_labels), labels (B,) with negative = ignored (rows a caller padded); B <= 1024"""
+    def update(self, logits, labels, logits_out=None, out_offset=0, pred=False, n_rows=None):
+        """logits (B, num_labels), labels (B,) with negative = ignored (rows a caller padded); B <= 1024.  `n_rows` (a batch padded to B rows): one
+        int32 device word, the rows that exist -- collecting metrics store and count those alone (ops.eval_accumulate_rows); metrics that do not
+        collect need no word, the padded rows' negative labels keep them out of every sum."""
         if self.collect_rows is None:
             return ops.eval_accumulate(logits, labels, self.acc, logits_out, out_offset, pred=pred)
         if logits_out is not None or pred:
             raise ValueError("MeldMetrics(collect_rows=...): the rows go to `results` / `truths` at the cursor; logits_out / pred are the other mode")
+        if n_rows is not None:
+            return ops.eval_accumulate_rows(logits, labels, self.acc, self.cursor, n_rows, self.results, self.truths)
         return ops.eval_accumulate_at(logits, labels, self.acc, self.cursor, self.results, self.truths)
 
     @staticmethod
@@ -144,6 +160,42 @@ class MeldMetrics:
         n = self.collected_count(self._host() if host is None else host, self.collect_rows)
         return self.results[:n], self.truths[:n]
 
+    def gather_merge(self, process_group=None):
+        """The shards of all ranks -> `self.merged`, the whole split, the same on every rank; returns it.  Every rank evaluated a contiguous block
+        of the dataset (parallel.eval_shard) into metrics of the same collect_rows (parallel.eval_collect_rows).  First one small all-gather of
+        `words` with collect_rows behind them: a rank built with another collect_rows raises ValueError on EVERY rank, before the large gather.
+        Then `results` and `truths` are gathered and ops.eval_merge (one launch) lays rank r's first cursor_r rows behind those of the ranks in
+        front of it and adds the accumulators, the loss sums in rank order.  gloo gathers host tensors, RCCL device tensors
+        (parallel.replicas_agree); nothing is copied to the host on RCCL, and nothing synchronises there.  World size 1, or no process group: no
+        collective, `merged` is filled by the same kernel with W = 1.  A shard that overflowed its buffers makes merged.collected() raise."""
+        if self.collect_rows is None:
+            raise ValueError("MeldMetrics.gather_merge: collecting metrics only (collect_rows=...): the merged split is made of the ranks' rows")
+        dev, nl, cap = self.words.device, self.num_labels, self.collect_rows
+        world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        if world > 64:
+            raise ValueError("MeldMetrics.gather_merge: at most 64 ranks (fmmt_eval_merge)")
+        if world == 1:
+            words, results, truths = self.words[None], self.results[None], self.truths[None]
+        else:
+            on_host = dist.get_backend(process_group) != "nccl"                # gloo gathers host tensors only; RCCL device tensors only
+
+            def gather(t):                                                     # (world,) + t.shape, rank order
+                t = t.cpu() if on_host else t
+                got = [torch.empty_like(t) for _ in range(world)]
+                dist.all_gather(got, t, group=process_group)
+                return torch.stack(got)
+            heads = gather(torch.cat((self.words, torch.tensor([cap], dtype=torch.int64, device=dev))))
+            caps = heads[:, -1].tolist()                                       # on RCCL a host read of W words: the check comes before the large gather
+            if any(c != caps[0] for c in caps):
+                raise ValueError(f"MeldMetrics.gather_merge: every rank builds its metrics with the same collect_rows (parallel.eval_collect_rows), "
+                                 f"the ranks hold {caps}")
+            words = heads[:, :-1].contiguous().to(dev)
+            results, truths = gather(self.results).to(dev), gather(self.truths).to(dev)
+        if self.merged is None or self.merged.collect_rows != world * cap:
+            self.merged = MeldMetrics(nl, dev, collect_rows=world * cap)
+        ops.eval_merge(words, results, truths, self.merged.words, self.merged.results, self.merged.truths)
+        return self.merged
+
 
 # ------------------------------------------------------------------------------------------------ one batch
 class _eval_mode:
@@ -174,10 +226,11 @@ def _check_padded_frames(frames, vision_inputs):
                          f"got {tuple(frames.shape)} (the compact (sum num_imgs, ...) tensor belongs to a step without frame_capacity)")
 
 
-def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_stream=None, shadows=None, frame_capacity=None):
+def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_stream=None, shadows=None, frame_capacity=None, n_rows=None):
     """the launches of one evaluation batch on the current stream (text encoder on `text_stream`, forked and joined, when given).  With a
     `frame_capacity` the batch's frames are the padded (B, Lv, ...) tensor: checked on the host where num_imgs lives there, packed on the device,
-    and everything up to the frame filter runs on `frame_capacity` rows.  Returns (logits, kept-frame mask, importance, frame counts or None)."""
+    and everything up to the frame filter runs on `frame_capacity` rows.  `n_rows`: the device word of a batch padded in its rows, handed to the
+    metric update.  Returns (logits, kept-frame mask, importance, frame counts or None)."""
     (ids, attn_mask, sep_mask, audio, audio_mask, vision_inputs, vision_mask, labels, frames, num_imgs, utt_idx) = batch
     dev = frames.device
     counts = None
@@ -214,7 +267,10 @@ def _forward_batch(swin, mm, args, batch, metrics, autocast_dtype, sample, text_
         text_mask.record_stream(main)
     with _autocast(autocast_dtype):
         logits = mm.fusion_branch(text_feat, text_mask, audio, audio_mask, vis_concat, new_mask)
-    metrics.update(logits, torch.as_tensor(labels, device=dev))
+    if n_rows is None:
+        metrics.update(logits, torch.as_tensor(labels, device=dev))
+    else:
+        metrics.update(logits, torch.as_tensor(labels, device=dev), n_rows=n_rows)
     return logits, new_mask, importance, counts
 
 
@@ -271,12 +327,23 @@ class GraphedEvalStep:
     largest, without a synchronisation.  A batch whose other shapes differ runs through EvalStep(frame_capacity=largest).  `replays` and
     `fallbacks` count the two paths on the host; `capacity` is the bucket of the last call, `frame_counts` / `importance` its outputs
     (`importance` has `capacity` rows, the first frame_counts[0] of them real).  Under gumbel="sample" the noise tensor has the bucket's
-    shape: see the module docstring."""
+    shape: see the module docstring.
+
+    `pad_rows` (default False: everything above, bit for bit; needs `frame_capacity`, ValueError otherwise, as on GraphedTargetStep): a batch
+    with 1 <= b <= B utterances whose other dimensions match is padded to the captured B by train_step.pad_target_batch (PAD_NOTE there: copies
+    of row 0, zero frames with num_imgs = 0, label -100) and REPLAYED in the bucket its real frames pick; no eager step, no second warm-up.  The
+    real row count goes into a static device word in front of the replay (a device fill, no synchronisation), and the captured metric update is
+    ops.eval_accumulate_rows when the metrics collect: the padded rows are neither stored nor counted and the cursor advances by b.  Metrics
+    that do not collect keep ops.eval_accumulate, which ignores the negative labels.  The step returns logits[:b], new_mask[:b].  `rows`: the
+    real rows of the last call; `padded_calls`: the calls that padded; `fallbacks` stays 0 for such a batch."""
 
     def __init__(self, swin_model, multimodal_model, args, batch, autocast_dtype=None, gumbel="sample", metrics=None, overlap_text=True, warmup_iters=2,
-                 frame_capacity=None):
+                 frame_capacity=None, pad_rows: bool = False):
         require_packet_capture_off("GraphedEvalStep")
         self.sample = _check_gumbel(gumbel)
+        self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
+        if self.pad_rows and frame_capacity is None:
+            raise ValueError("pad_rows: only with frame_capacity (compact frames change their shape with the batch's rows)")
         self.swin, self.mm, self.args, self.autocast_dtype = swin_model, multimodal_model, args, autocast_dtype
         self.buckets = frame_buckets(frame_capacity)
         if self.buckets is not None:
@@ -288,6 +355,8 @@ class GraphedEvalStep:
         self.metrics = metrics if metrics is not None else MeldMetrics(swin_model.num_labels, dev)
         self.eager = EvalStep(swin_model, multimodal_model, args, autocast_dtype, gumbel, self.metrics, frame_capacity=self.buckets[-1] if self.buckets else None)
         self.static = [t.clone() if torch.is_tensor(t) else torch.as_tensor(t, device=dev) for t in batch]
+        # the rows of the batch that exist, re-read by the captured metric update on every replay; without pad_rows no such word and no such kernel
+        self.n_rows = torch.full((1,), len(batch[7]), dtype=torch.int32, device=dev) if self.pad_rows else None
         cap = distinct_stream(dev)
         self.text_stream = distinct_stream(dev, (cap,)) if overlap_text else None
         collect = getattr(self.metrics, "collect_rows", None)                  # the warm-up passes count into this one, through the same kernel
@@ -300,14 +369,14 @@ class GraphedEvalStep:
                 with warmup_undone([], dev, cap):                              # an evaluation pass moves nothing but the generator
                     for _ in range(max(1, warmup_iters)):                      # lazy initialisations, the shadow cache the pins are made from
                         scratch.reset()
-                        _forward_batch(self.swin, self.mm, args, self.static, scratch, autocast_dtype, self.sample, frame_capacity=c)
+                        _forward_batch(self.swin, self.mm, args, self.static, scratch, autocast_dtype, self.sample, frame_capacity=c, n_rows=self.n_rows)
                 if not self.graphs:
                     self.shadows = _pin_shadows([self.swin, self.mm])
                 graph = torch.cuda.CUDAGraph()
                 with capture_window(), ops.pinned_scope(self.shadows):
                     with torch.cuda.graph(graph, stream=cap):
                         outs = _forward_batch(self.swin, self.mm, args, self.static, self.metrics, autocast_dtype, self.sample, self.text_stream,
-                                              self.shadows, frame_capacity=c)
+                                              self.shadows, frame_capacity=c, n_rows=self.n_rows)
                 self.graphs[c] = (graph, outs)
                 _KEEP_GRAPHS.append((graph,))
             if self.buckets:
@@ -315,11 +384,16 @@ class GraphedEvalStep:
         self.graph, (self.logits, self.new_mask, self.importance, _) = self.graphs[self.buckets[-1] if self.buckets else None]
 
     def __call__(self, batch):
+        rows = self.static[7].shape[0]
+        b, given = rows, batch
+        if self.pad_rows and len(batch) == len(self.static) and 1 <= len(batch[7]) < rows:
+            b, batch = len(batch[7]), pad_target_batch(batch, rows)
         try:
             check_static_shapes(self.static, batch, "GraphedEvalStep")
         except ValueError:
             if len(batch) != len(self.static):
                 raise
+            b, batch = rows, given                                 # not a short batch of the captured shapes: the launch-by-launch step, unpadded
             if self.buckets:
                 _check_padded_frames(torch.as_tensor(batch[8]), torch.as_tensor(batch[5]))     # the compact tensor is an error, not "another shape"
             out = self.eager(batch)
@@ -331,8 +405,14 @@ class GraphedEvalStep:
         copy_into_static(self.static, batch, "GraphedEvalStep")
         self.graph, (self.logits, self.new_mask, self.importance, self.frame_counts) = self.graphs[c]
         self.capacity = c
+        if self.pad_rows:
+            self.n_rows.fill_(b)                                   # a device fill: no host synchronisation
         self.graph.replay()
         self.replays += 1
+        self.rows = b
+        self.padded_calls += int(b != rows)
+        if b != rows:
+            return self.logits[:b], self.new_mask[:b]
         return self.logits, self.new_mask
 
 
@@ -352,7 +432,7 @@ class UnimodalEvalStep:
         return logits
 
 
-def evaluate(step, loader):
+def evaluate(step, loader, sharded=False, process_group=None):
     """A whole split through `step` (EvalStep / GraphedEvalStep / UnimodalEvalStep): (avg_loss, results, truths) as multimodal_evaluate /
     unimodal_evaluate return them -- results = the concatenated logits, truths = the concatenated labels, both left on the device.  The one
     host synchronisation is the final copy of the accumulators; step.metrics.result() afterwards has the F1 scores of the same split.
@@ -360,8 +440,24 @@ def evaluate(step, loader):
 
     When step.metrics collects (MeldMetrics(collect_rows=...)), nothing is cloned per batch: the metric update inside the step has stored every
     row, and results / truths are `collected()` -- views of the metrics' buffers, valid until its next reset() or update(); ValueError when the
-    split had more rows than collect_rows.  Cursor and accumulators come to the host in the same single copy."""
+    split had more rows than collect_rows.  Cursor and accumulators come to the host in the same single copy.
+
+    `sharded=True` (collecting metrics only, ValueError otherwise): `loader` is this rank's shard of the split -- the rows parallel.eval_shard gives
+    it, in batches the single-rank loader would have formed; an empty one for a rank without rows -- and step.metrics was built with
+    collect_rows = parallel.eval_collect_rows(...).  The batches run with no collective between them, so ranks may run different numbers of them;
+    then MeldMetrics.gather_merge(process_group) makes the whole split on every rank and (avg_loss, results, truths) are the WHOLE split's, from
+    step.metrics.merged, the same values on every rank, in dataset order.  step.metrics.result() stays the rank's own, step.metrics.merged.result()
+    is the split's.  Still one device-to-host copy per split on RCCL behind the W words gather_merge reads."""
     step.metrics.reset()
+    if sharded:
+        if getattr(step.metrics, "collect_rows", None) is None:
+            raise ValueError("evaluate(sharded=True): the step's metrics collect the split (MeldMetrics(collect_rows=parallel.eval_collect_rows(...)))")
+        for batch in loader:
+            step(batch)
+        merged = step.metrics.gather_merge(process_group)
+        host = merged._host()
+        nl = merged.num_labels
+        return (merged.summarise(host[:2 + nl * nl], nl).avg_loss,) + merged.collected(host)
     if getattr(step.metrics, "collect_rows", None) is not None:
         for batch in loader:
             step(batch)

@@ -1915,37 +1915,82 @@ def eval_accumulate(logits, labels, acc, logits_out=None, out_offset=0, pred=Tru
     return out
 
 
-def eval_accumulate_at(logits, labels, acc, cursor, logits_out, labels_out, pred_out=None):
-    """fmmt_eval_accumulate_at: eval_accumulate with the destination row in a DEVICE word, so that a captured graph collects a split.  cursor: int64
-    CUDA tensor of one word; row i of the batch goes to logits_out[cursor + i] ((capacity, NL) fp32), labels_out[cursor + i] ((capacity,) int64)
-    and pred_out[cursor + i] ((capacity,) int32, optional); rows at or behind the capacity are counted and stored nowhere; cursor += B on the
-    device (cursor > capacity afterwards: the split overflowed).  The accumulators get the bits eval_accumulate gives them.  Returns None."""
-    _need_cuda(logits, "eval_accumulate_at")
-    _no_grad_only("eval_accumulate_at", logits)
+def _eval_collect_args(who, logits, labels, acc, cursor, logits_out, labels_out, pred_out):
+    """the checks eval_accumulate_at and eval_accumulate_rows share -> (logits, labels, address of acc, capacity, B, NL)"""
+    _need_cuda(logits, who)
+    _no_grad_only(who, logits)
     if logits.dim() != 2 or labels.shape != (logits.shape[0],):
-        raise _lib.FmmtError("eval_accumulate_at: logits (B, NL), labels (B,)")
+        raise _lib.FmmtError(f"{who}: logits (B, NL), labels (B,)")
     B, NL = logits.shape
     dev = logits.device
     if acc.dtype != torch.int64 or acc.numel() != 2 + NL * NL or not acc.is_contiguous() or acc.device != dev:
-        raise _lib.FmmtError(f"eval_accumulate_at: acc must be a contiguous int64 CUDA tensor of {2 + NL * NL} words")
+        raise _lib.FmmtError(f"{who}: acc must be a contiguous int64 CUDA tensor of {2 + NL * NL} words")
     if not torch.is_tensor(cursor) or cursor.dtype != torch.int64 or cursor.numel() != 1 or cursor.device != dev:
-        raise _lib.FmmtError("eval_accumulate_at: cursor must be an int64 tensor of one word on the logits' device")
+        raise _lib.FmmtError(f"{who}: cursor must be an int64 tensor of one word on the logits' device")
     if (not torch.is_tensor(logits_out) or logits_out.dtype != torch.float32 or logits_out.dim() != 2 or logits_out.shape[1] != NL
             or not logits_out.is_contiguous() or logits_out.device != dev):
-        raise _lib.FmmtError("eval_accumulate_at: logits_out must be a contiguous fp32 (capacity, NL) tensor on the logits' device")
+        raise _lib.FmmtError(f"{who}: logits_out must be a contiguous fp32 (capacity, NL) tensor on the logits' device")
     cap = logits_out.shape[0]
     for name, t, dt in (("labels_out", labels_out, torch.int64), ("pred_out", pred_out, torch.int32)):
         if t is None and name == "pred_out":
             continue
         if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != (cap,) or not t.is_contiguous() or t.device != dev:
-            raise _lib.FmmtError(f"eval_accumulate_at: {name} must be a contiguous {dt} ({cap},) tensor on the logits' device (logits_out's rows)")
+            raise _lib.FmmtError(f"{who}: {name} must be a contiguous {dt} ({cap},) tensor on the logits' device (logits_out's rows)")
     lg = logits.detach()
     if lg.stride(1) != 1:
         lg = lg.contiguous()
     lab = labels.detach().to(device=dev, dtype=torch.int64).contiguous()
-    a = acc.data_ptr()
+    return lg, lab, acc.data_ptr(), cap, B, NL
+
+
+def eval_accumulate_at(logits, labels, acc, cursor, logits_out, labels_out, pred_out=None):
+    """fmmt_eval_accumulate_at: eval_accumulate with the destination row in a DEVICE word, so that a captured graph collects a split.  cursor: int64
+    CUDA tensor of one word; row i of the batch goes to logits_out[cursor + i] ((capacity, NL) fp32), labels_out[cursor + i] ((capacity,) int64)
+    and pred_out[cursor + i] ((capacity,) int32, optional); rows at or behind the capacity are counted and stored nowhere; cursor += B on the
+    device (cursor > capacity afterwards: the split overflowed).  The accumulators get the bits eval_accumulate gives them.  Returns None."""
+    lg, lab, a, cap, B, NL = _eval_collect_args("eval_accumulate_at", logits, labels, acc, cursor, logits_out, labels_out, pred_out)
     check(_lib.load().fmmt_eval_accumulate_at(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), a, a + 8, a + 16, _p(cursor), _p(logits_out),
                                               _p(labels_out), _p(pred_out), int(cap), _st()), f"fmmt_eval_accumulate_at(B={B},NL={NL},capacity={cap})")
+
+
+def eval_accumulate_rows(logits, labels, acc, cursor, n_rows, logits_out, labels_out, pred_out=None):
+    """fmmt_eval_accumulate_rows: eval_accumulate_at for a batch PADDED to (B, NL), the number of rows that exist in a device word -- n_rows: int32
+    CUDA tensor of one word, b = its value clamped to [0, B].  Rows i >= b are neither stored nor counted, whatever their label; cursor += b on the
+    device.  With n_rows == B: the bits of eval_accumulate_at.  A captured graph re-reads the word on every replay.  Returns None."""
+    lg, lab, a, cap, B, NL = _eval_collect_args("eval_accumulate_rows", logits, labels, acc, cursor, logits_out, labels_out, pred_out)
+    if not torch.is_tensor(n_rows) or n_rows.dtype != torch.int32 or n_rows.numel() != 1 or n_rows.device != lg.device:
+        raise _lib.FmmtError("eval_accumulate_rows: n_rows must be an int32 tensor of one word on the logits' device")
+    check(_lib.load().fmmt_eval_accumulate_rows(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), a, a + 8, a + 16, _p(cursor), _p(n_rows),
+                                                _p(logits_out), _p(labels_out), _p(pred_out), int(cap), _st()),
+          f"fmmt_eval_accumulate_rows(B={B},NL={NL},capacity={cap})")
+
+
+def eval_merge(words, results, truths, words_out, results_out, truths_out):
+    """fmmt_eval_merge: W gathered shards of an evaluation split -> the split, one launch.  words (W, 2 + NL * NL + 1) int64 (per rank: loss-sum bits,
+    count, confusion, cursor -- MeldMetrics.words), results (W, cap, NL) fp32, truths (W, cap) int64; words_out (2 + NL * NL + 1,), results_out
+    (out_cap, NL), truths_out (out_cap,) receive the merged split in MeldMetrics's layout: rank r's first min(cursor_r, cap) rows behind those of the
+    ranks in front of it, rows behind the total untouched, the loss sums added in rank order, cursor_out > out_cap when a rank or the outputs
+    overflowed (include/fmmt_eval_shard.h).  All contiguous, on one device; 1 <= W <= 64.  Returns None."""
+    _need_cuda(words, "eval_merge")
+    dev = words.device
+    if results.dim() != 3 or results.dtype != torch.float32:
+        raise _lib.FmmtError("eval_merge: results (W, cap, NL) fp32")
+    W, cap, NL = results.shape
+    nw = 2 + NL * NL + 1
+    if results_out.dim() != 2 or results_out.dtype != torch.float32 or results_out.shape[1] != NL:
+        raise _lib.FmmtError(f"eval_merge: results_out (out_cap, {NL}) fp32")
+    out_cap = results_out.shape[0]
+    for name, t, dt, shape in (("words", words, torch.int64, (W, nw)), ("results", results, torch.float32, (W, cap, NL)), ("truths", truths, torch.int64, (W, cap)),
+                               ("words_out", words_out, torch.int64, (nw,)), ("results_out", results_out, torch.float32, (out_cap, NL)),
+                               ("truths_out", truths_out, torch.int64, (out_cap,))):
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise _lib.FmmtError(f"eval_merge: {name} must be a contiguous {dt} {shape} tensor on the device of `words`")
+    if not 1 <= W <= 64 or not 1 <= NL <= 8:
+        raise _lib.FmmtError("eval_merge: 1 <= W <= 64 ranks, 1 <= NL <= 8 classes")
+    # an empty buffer has no address: the kernel touches neither at cap == 0 / out_cap == 0, the entry point wants non-NULL pointers
+    check(_lib.load().fmmt_eval_merge(W, NL, int(cap), int(out_cap), _p(words), _p(results) or _p(words), _p(truths) or _p(words), _p(words_out),
+                                      _p(results_out) or _p(words_out), _p(truths_out) or _p(words_out), _st()),
+          f"fmmt_eval_merge(W={W},NL={NL},cap={cap},out_cap={out_cap})")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -275,6 +275,33 @@ def replicas_agree(digest, process_group=None):
     return got
 
 
+def eval_shard(n_rows: int, batch_size: int, rank=None, world=None) -> range:
+    """The rows of an evaluation split of `n_rows` rows that `rank` of `world` evaluates (default: this process's rank and the world size of the
+    default process group; 0 of 1 without one): contiguous and in WHOLE batches -- per = ceil(ceil(n_rows / batch_size) / world) batches per rank,
+    rank r owns rows [r * per * batch_size, min((r + 1) * per * batch_size, n_rows)).  Every batch a rank forms from its range in order is a batch
+    the single-rank loader would have formed; only the last non-empty rank ends short, and a late rank may be empty (an empty range).
+    Ranges in rank order are the dataset's order, which is what MeldMetrics.gather_merge relies on."""
+    if world is None:
+        world = dist.get_world_size() if dist.is_initialized() else 1
+    if rank is None:
+        rank = dist.get_rank() if dist.is_initialized() else 0
+    n, bs, rank, world = int(n_rows), int(batch_size), int(rank), int(world)
+    if n < 0 or bs < 1 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"eval_shard: n_rows >= 0, batch_size >= 1, 0 <= rank < world, got n_rows={n}, batch_size={bs}, rank={rank}, world={world}")
+    per = eval_collect_rows(n, bs, world)
+    return range(rank * per, min((rank + 1) * per, n))                     # an empty rank: a start behind n, still a multiple of the batch size
+
+
+def eval_collect_rows(n_rows: int, batch_size: int, world: int) -> int:
+    """The `collect_rows` EVERY rank builds its MeldMetrics with for a split sharded by eval_shard: the rows of the largest shard,
+    ceil(ceil(n_rows / batch_size) / world) * batch_size"""
+    n, bs, world = int(n_rows), int(batch_size), int(world)
+    if n < 0 or bs < 1 or world < 1:
+        raise ValueError(f"eval_collect_rows: n_rows >= 0, batch_size >= 1, world >= 1, got n_rows={n}, batch_size={bs}, world={world}")
+    batches = (n + bs - 1) // bs
+    return (batches + world - 1) // world * bs
+
+
 def shard_utterances(n_global: int, rank: int, world: int):
     """contiguous split of a global batch of utterances across ranks"""
     per = (n_global + world - 1) // world

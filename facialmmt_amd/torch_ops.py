@@ -22,6 +22,8 @@ Registered (forward ops return what their backward needs as extra outputs, as cu
     fmmt::emotion_head(feats, w1, b1, w2, b2, gumbel?, tau) -> (preds, importance)         evaluation: Swin's target-task head + Gumbel-softmax + importance (no gradient)
     fmmt::eval_accumulate(logits, labels, acc!, logits_out!?, out_offset) -> pred           evaluation: loss sum / count / confusion matrix accumulated on the device (no gradient)
     fmmt::eval_accumulate_at(logits, labels, acc!, cursor!, logits_out!, labels_out!, pred_out!?) -> ()   the same update, the batch's rows kept at a device-held row index that it advances
+    fmmt::eval_accumulate_rows(logits, labels, acc!, cursor!, n_rows, logits_out!, labels_out!, pred_out!?) -> ()   that update for a padded batch: a device word says how many rows exist
+    fmmt::eval_merge(words, results, truths, words_out!, results_out!, truths_out!) -> ()   W gathered shards of a split (accumulators, cursors, rows) -> the split in rank order
 
 The nn.Modules of facialmmt_amd/modules keep using ops.py (fewer dispatcher hops per launch); tests/test_gpu_torch_ops.py
 holds the two front ends bit-identical, forward and backward, and runs torch.library.opcheck on each operator."""
@@ -543,4 +545,25 @@ def eval_accumulate_at(logits: Tensor, labels: Tensor, acc: Tensor, cursor: Tens
 
 @eval_accumulate_at.register_fake
 def _(logits, labels, acc, cursor, logits_out, labels_out, pred_out):
+    return None
+
+
+@torch.library.custom_op(f"{_LIB}::eval_accumulate_rows", mutates_args=("acc", "cursor", "logits_out", "labels_out", "pred_out"), device_types="cuda")
+def eval_accumulate_rows(logits: Tensor, labels: Tensor, acc: Tensor, cursor: Tensor, n_rows: Tensor, logits_out: Tensor, labels_out: Tensor,
+                         pred_out: Optional[Tensor]) -> None:
+    ops.eval_accumulate_rows(logits, labels, acc, cursor, n_rows, logits_out, labels_out, pred_out)
+
+
+@eval_accumulate_rows.register_fake
+def _(logits, labels, acc, cursor, n_rows, logits_out, labels_out, pred_out):
+    return None
+
+
+@torch.library.custom_op(f"{_LIB}::eval_merge", mutates_args=("words_out", "results_out", "truths_out"), device_types="cuda")
+def eval_merge(words: Tensor, results: Tensor, truths: Tensor, words_out: Tensor, results_out: Tensor, truths_out: Tensor) -> None:
+    ops.eval_merge(words, results, truths, words_out, results_out, truths_out)
+
+
+@eval_merge.register_fake
+def _(words, results, truths, words_out, results_out, truths_out):
     return None

@@ -524,6 +524,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_guard.h"
 /* The replica digest over the optimizer's descriptor table (fmmt_param_digest): likewise, held to _lib.DIGEST_SIGNATURES. */
 #include "fmmt_digest.h"
+/* An evaluation split sharded over ranks (the collecting metric update with a device-held row count, the merge of the gathered shards): likewise, held to _lib.EVAL_SHARD_SIGNATURES. */
+#include "fmmt_eval_shard.h"
 
 #ifdef __cplusplus
 }
