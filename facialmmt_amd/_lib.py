@@ -140,6 +140,17 @@ EVAL_SHARD_SIGNATURES = {
     "fmmt_eval_merge": (_i, [_i, _i, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p, _p]),
 }
 
+# include/fmmt_jitter.h, one to one: a ninth table and header for the same reason -- the uint8 pre-step pair with the per-frame ColorJitter table and
+# the contrast statistic's scratch behind `lut_dev` (tests/test_color_jitter_cpu.py::test_jitter_header_signatures_and_library_agree holds table, header and library together)
+JITTER_SIGNATURES = {
+    "fmmt_jitter_table_check": (_i, [_p, _i]),
+    "fmmt_patch_embed_u8_jitter": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "fmmt_patch_embed_u8_jitter_ln_fwd": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
+}
+# the record layout (include/fmmt_jitter.h FMMT_JITTER_*): the one place Python states it; augment.ColorJitter builds tables through these
+JITTER_WORDS, JITTER_BANDS = 8, 56
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE, JITTER_NONE = 0, 1, 2, 3, 4
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -160,7 +171,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1617,9 +1617,21 @@ def resize_tables(mode: str, in_size: int, device):
     return _RESIZE_TABLES[key]
 
 
-def patch_embed_u8(img_u8: torch.Tensor, mode: str, dtype) -> torch.Tensor:
+def _jitter_table(jitter, img_u8, what):
+    """the (n, 8) int32 device table of augment.ColorJitter (include/fmmt_jitter.h), checked against the frames it is for"""
+    if not torch.is_tensor(jitter) or jitter.dtype != torch.int32 or tuple(jitter.shape) != (img_u8.shape[0], _lib.JITTER_WORDS):
+        got = f"{tuple(jitter.shape)} {jitter.dtype}" if torch.is_tensor(jitter) else type(jitter).__name__
+        raise ValueError(f"{what}: the ColorJitter table is ({img_u8.shape[0]}, {_lib.JITTER_WORDS}) int32, one record per frame, got {got}")
+    if jitter.device != img_u8.device:
+        raise ValueError(f"{what}: the ColorJitter table is on {jitter.device}, the frames on {img_u8.device}")
+    return jitter.contiguous()
+
+
+def patch_embed_u8(img_u8: torch.Tensor, mode: str, dtype, jitter=None) -> torch.Tensor:
     """(n, S, S, 3) uint8 crops (image layout) -> (n*3136, 48) patch matrix of Normalize(ToTensor(resize_224(img))):
-    the input pre-step fused into PatchEmbed's gather (no gradient: the input is integer data)."""
+    the input pre-step fused into PatchEmbed's gather (no gradient: the input is integer data).
+    jitter: None, or the (n, 8) int32 table of augment.ColorJitter -- the frame's brightness / contrast / saturation / hue operations on the resized
+    bytes, in front of ToTensor (fmmt_patch_embed_u8_jitter: two launches; None is the call above, through the entry point above)."""
     _need_cuda(img_u8, "patch_embed_u8")
     if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != img_u8.shape[2] or img_u8.shape[3] != 3:
         raise ValueError(f"patch_embed_u8 expects (n, S, S, 3) uint8 crops, got {tuple(img_u8.shape)} {img_u8.dtype}")
@@ -1627,6 +1639,12 @@ def patch_embed_u8(img_u8: torch.Tensor, mode: str, dtype) -> torch.Tensor:
     n, S = img_u8.shape[0], img_u8.shape[1]
     code, tab, lut = resize_tables(mode, S, img_u8.device)
     cols = torch.empty((n * 3136, 48), dtype=dtype, device=img_u8.device)
+    if jitter is not None:
+        jitter = _jitter_table(jitter, img_u8, "patch_embed_u8")
+        partial = torch.empty((n, _lib.JITTER_BANDS), dtype=torch.int32, device=img_u8.device)
+        rc = _lib.load().fmmt_patch_embed_u8_jitter(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(jitter), _p(partial), _p(cols), _st())
+        check(rc, f"fmmt_patch_embed_u8_jitter(n={n},S={S},{mode})")
+        return cols
     rc = _lib.load().fmmt_patch_embed_u8(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(cols), _st())
     check(rc, f"fmmt_patch_embed_u8(n={n},S={S},{mode})")
     return cols
@@ -1642,7 +1660,7 @@ class PatchEmbedU8LnFn(Function):
     backward = PatchProjLnFn's (the input is integer data: no input gradient)."""
 
     @staticmethod
-    def forward(ctx, img_u8, mode, weight, bias, gamma, beta, eps, dtype, grad_on=True):
+    def forward(ctx, img_u8, mode, weight, bias, gamma, beta, eps, dtype, grad_on=True, jitter=None):
         _need_cuda(img_u8, "patch_embed_u8_ln")
         if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != img_u8.shape[2] or img_u8.shape[3] != 3:
             raise ValueError(f"patch_embed_u8 expects (n, S, S, 3) uint8 crops, got {tuple(img_u8.shape)} {img_u8.dtype}")
@@ -1658,10 +1676,19 @@ class PatchEmbedU8LnFn(Function):
         x_pre = torch.empty_like(y) if train else None
         mean = torch.empty(M, dtype=torch.float32, device=dev) if train else None
         rstd = torch.empty(M, dtype=torch.float32, device=dev) if train else None
-        rc = _lib.load().fmmt_patch_embed_u8_ln_fwd(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(_lp(weight, dtype)),
-                                                    _p(bias.detach().float().contiguous() if bias is not None else None), _p(g), _p(b), float(eps),
-                                                    _p(cols), _p(x_pre), _p(y), _p(mean), _p(rstd), _st())
-        check(rc, f"fmmt_patch_embed_u8_ln_fwd(n={n},S={S},{mode})")
+        bias32 = bias.detach().float().contiguous() if bias is not None else None
+        if jitter is not None:           # augment.ColorJitter's table: the same launch behind the contrast statistic's (fmmt_patch_embed_u8_jitter_ln_fwd)
+            jitter = _jitter_table(jitter, img_u8, "patch_embed_u8_ln")
+            partial = torch.empty((n, _lib.JITTER_BANDS), dtype=torch.int32, device=dev)
+            rc = _lib.load().fmmt_patch_embed_u8_jitter_ln_fwd(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(jitter), _p(partial),
+                                                               _p(_lp(weight, dtype)), _p(bias32), _p(g), _p(b), float(eps),
+                                                               _p(cols), _p(x_pre), _p(y), _p(mean), _p(rstd), _st())
+            check(rc, f"fmmt_patch_embed_u8_jitter_ln_fwd(n={n},S={S},{mode})")
+        else:
+            rc = _lib.load().fmmt_patch_embed_u8_ln_fwd(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(_lp(weight, dtype)),
+                                                        _p(bias32), _p(g), _p(b), float(eps),
+                                                        _p(cols), _p(x_pre), _p(y), _p(mean), _p(rstd), _st())
+            check(rc, f"fmmt_patch_embed_u8_ln_fwd(n={n},S={S},{mode})")
         ctx.save_for_backward(cols, weight, x_pre, mean, rstd, g)
         ctx.has_bias = bias is not None
         return y
@@ -1680,7 +1707,7 @@ class PatchEmbedU8LnFn(Function):
         check(lib.fmmt_layernorm_bwd(dtype_code(dy.dtype), M, C, _p(dy), _p(x_pre), _p(mean), _p(rstd), _p(g), None, _p(dxp), _p(dg), _p(db), 0,
                                      _p(ws), nbytes, _st()), f"fmmt_layernorm_bwd(patch embed, M={M})")
         dw, dbias = wgrad_raw(dxp, cols, ctx.has_bias)
-        return None, None, dw.view_as(weight), dbias, dg, db, None, None, None
+        return None, None, dw.view_as(weight), dbias, dg, db, None, None, None, None
 
 
 def patch_embed_u8_ln_fusable(img_u8, weight, norm, dtype):
@@ -1689,8 +1716,8 @@ def patch_embed_u8_ln_fusable(img_u8, weight, norm, dtype):
             and not any(t.data_ptr() % 16 for t in (weight, norm.weight, norm.bias)))
 
 
-def patch_embed_u8_ln(img_u8, mode, weight, bias, gamma, beta, eps, dtype):
-    return PatchEmbedU8LnFn.apply(img_u8, mode, weight, bias, gamma, beta, eps, dtype, torch.is_grad_enabled())
+def patch_embed_u8_ln(img_u8, mode, weight, bias, gamma, beta, eps, dtype, jitter=None):
+    return PatchEmbedU8LnFn.apply(img_u8, mode, weight, bias, gamma, beta, eps, dtype, torch.is_grad_enabled(), jitter)
 
 
 def batch_norm_1d_fwd_raw(x, g, b, running_mean, running_var, momentum, eps, training):

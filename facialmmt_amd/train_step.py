@@ -298,6 +298,18 @@ def graph_multimodal(mm, sample_args, autocast_dtype=None, overlap_text=True, pa
 SKIP_NOTE = "Swin's target-step gradients are never read (train.py:20,33,140-143): 'skip' does not compute them"
 
 
+def _check_color_jitter(color_jitter):
+    from .augment import ColorJitter
+    if color_jitter is not None and not isinstance(color_jitter, ColorJitter):
+        raise TypeError(f"color_jitter: an augment.ColorJitter or None, got {type(color_jitter).__name__}")
+    return color_jitter
+
+
+def _need_u8_frames(frames):
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"color_jitter works on the uint8 crops the pre-step resizes (frames (.., S, S, 3) uint8), got {frames.dtype} frames")
+
+
 class TargetStep(StepState):
     """Swin (train mode, Gumbel-softmax head) -> frame filter -> multimodal model -> CE -> backward ->
     (every `accumulation_steps`) clip + AdamW + schedule, as train.py:46-143.  Only the multimodal
@@ -306,9 +318,11 @@ class TargetStep(StepState):
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "target", ("swin", "mm"), "trg_accumulation_steps"
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, autocast_dtype=None, ddp_model=None, averager=None,
-                 discarded_swin_gradients="compute", frame_capacity=None):
+                 discarded_swin_gradients="compute", frame_capacity=None, color_jitter=None):
         """Data parallel: pass `averager` (parallel.GradientAverager over the multimodal parameters) or, alternatively,
         `ddp_model` (the module wrapped by torch's DistributedDataParallel).
+        `color_jitter` (an augment.ColorJitter; None: no augmentation): the MELD train transform (utils/dataset.py:35-39,62-63) on the uint8 frames,
+        inside the pre-step -- every call draws a table from the device generator for the frames Swin runs on and keeps it in `last_jitter`.
         `discarded_swin_gradients`: "compute" (default, what the reference executes) or "skip" -- see SKIP_NOTE.
         `frame_capacity` (None: `frames` is the compact (sum num_imgs, ...) tensor): the batch carries `frames` as the loader pads them,
         (B, Lv, ...), and the step packs them on the device into `frame_capacity` rows (ops.pack_frames), runs Swin on all of them with the
@@ -332,6 +346,8 @@ class TargetStep(StepState):
         self.autocast_dtype = autocast_dtype
         self.i_batch = 0
         self.host_ms = {}          # cumulative host-side enqueue time per phase (no device sync)
+        self.color_jitter = _check_color_jitter(color_jitter)
+        self.last_jitter = None                              # color_jitter: the table of the last call (device, int32 (frames, 8))
 
     def start_epoch(self):
         """As the reference at the top of each epoch (train.py:52,54): gradients zeroed, micro-batch count restarted, so a
@@ -363,6 +379,8 @@ class TargetStep(StepState):
         if evs is not None:
             mark("start")
         from .parallel import GradientAverager, accumulate
+        if self.color_jitter is not None:
+            _need_u8_frames(frames)                          # ValueError before anything is launched
         n_valid, swin_kw = None, {}
         if self.capacities is not None:
             cap = frame_bucket(num_imgs, frames.shape[1], self.capacities)     # ValueError before anything is launched
@@ -381,6 +399,8 @@ class TargetStep(StepState):
                     self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
             else:
                 self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
+        if self.color_jitter is not None:                   # one record per frame Swin runs on (packed: per slot of the capacity), drawn just ahead of Swin
+            self.last_jitter = swin_kw["jitter"] = self.color_jitter.draw(frames.shape[0], frames.device)
         if self.skip_swin_bwd:
             with torch.no_grad():
                 preds = self.swin(frames, is_trg_task=True, **swin_kw)
@@ -1306,7 +1326,7 @@ class GraphedTargetStep(StepState):
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
                  swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None,
-                 pad_rows: bool = False, skip_nonfinite: bool = False):
+                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None):
         """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
@@ -1345,7 +1365,12 @@ class GraphedTargetStep(StepState):
         Needs frame_capacity (compact frames change shape with the batch: ValueError); not with pipeline_swin / branch_graphs / fork_streams
         (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.  Under an active
         averager ranks may hold different numbers of real rows: pass `global_rows` to the call (ROW_WEIGHT_NOTE).
-        `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too; several capacities share the one monitor."""
+        `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too; several capacities share the one monitor.
+        `color_jitter` (an augment.ColorJitter; None: no augmentation, the launches of before): the MELD train transform (utils/dataset.py:35-39,
+        62-63) inside the uint8 pre-step.  The draw of the per-frame table is PART of every capture in front of Swin's forward (every capacity's, and
+        graph S of pipeline_swin): one torch.rand on the device generator and elementwise launches, so every replay jitters anew and a resumed
+        generator walks the same tables.  With a frame capacity the table has that many records (padded slots are jittered like any bytes: nothing
+        reads them).  `last_jitter`: the table of the last Swin forward replayed (device, int32 (frames, 8)).  Frames must be uint8 (ValueError)."""
         from . import ops
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
@@ -1383,6 +1408,11 @@ class GraphedTargetStep(StepState):
         self.i_batch = 0
         self.timing = None
         dev = batch[0].device
+        self.color_jitter, self._jitter_buf = _check_color_jitter(color_jitter), None
+        if self.color_jitter is not None:
+            _need_u8_frames(torch.as_tensor(batch[8]))
+            rows = self.frame_capacity if self.frame_capacity is not None else batch[8].shape[0]
+            self._jitter_buf = torch.empty((rows, 8), dtype=torch.int32, device=dev)      # static: every capture's draw lands in its first rows
         # every batch entry becomes a static device tensor: a python list / int baked into the capture would silently be reused
         # by every replay (the reference's collate hands num_imgs and the utterance index over as lists)
         self.static = [t.clone() if torch.is_tensor(t) else torch.as_tensor(t, device=dev) for t in batch]
@@ -1596,7 +1626,7 @@ class GraphedTargetStep(StepState):
         with torch.cuda.stream(ts):
             feat, tmask = self._text_forward(refresh=False)
         with torch.cuda.stream(ss):
-            preds = self.swin(frames, is_trg_task=True)
+            preds = self.swin(frames, is_trg_task=True, **self._draw_jitter(frames.shape[0]))
         cap.wait_stream(ts)
         cap.wait_stream(ss)
         for t in (feat, tmask, preds):
@@ -1694,13 +1724,28 @@ class GraphedTargetStep(StepState):
         if self.monitor is not None:
             self.monitor.loss(loss.detach(), self.args.trg_accumulation_steps)
 
+    @property
+    def last_jitter(self):
+        """color_jitter: the table the last Swin forward ran with (a view of the static buffer the captured draws write)"""
+        if self._jitter_buf is None:
+            return None
+        return self._jitter_buf[:self.capacity if self.capacities is not None and self.capacity is not None else self._jitter_buf.shape[0]]
+
+    def _draw_jitter(self, n):
+        """color_jitter: {} or the keyword that hands Swin a fresh table for n frames (a draw on the device generator, captured with the forward)"""
+        if self.color_jitter is None:
+            return {}
+        table = self._jitter_buf[:n]
+        table.copy_(self.color_jitter.draw(n, table.device))
+        return {"jitter": table}
+
     def _swin_preds(self, frames, num_imgs):
         """Swin's target-task forward on the step's frames; with a frame capacity: packed on the device first (-> self.frame_counts)"""
         if self.frame_capacity is None:
-            return self.swin(frames, is_trg_task=True)
+            return self.swin(frames, is_trg_task=True, **self._draw_jitter(frames.shape[0]))
         from . import ops
         packed, self.frame_counts = ops.pack_frames(frames, num_imgs, self._cap, counts=self._counts_buf)
-        return self.swin(packed, is_trg_task=True, n_valid=self.frame_counts)
+        return self.swin(packed, is_trg_task=True, n_valid=self.frame_counts, **self._draw_jitter(self._cap))
 
     def _use_capacity(self, c, batch):
         """several capacities: the next warm-up / capture packs into `c`, on the sample batch's counts cut down to fit it"""
@@ -1712,7 +1757,7 @@ class GraphedTargetStep(StepState):
         """pipeline_swin, graph S: Swin's forward alone (its bf16 shadows refreshed at the head: an auxiliary step may have moved the weights)"""
         if self.swin_shadows is not None:
             self.swin_shadows.refresh()
-        return self.swin(frames, is_trg_task=True)
+        return self.swin(frames, is_trg_task=True, **self._draw_jitter(frames.shape[0]))
 
     def _fwd_bwd_multimodal(self, whole=False, preds=None):
         """forward of everything + backward of the loss down to (a) the multimodal parameters and (b) Swin's output; returns

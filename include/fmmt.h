@@ -526,6 +526,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_digest.h"
 /* An evaluation split sharded over ranks (the collecting metric update with a device-held row count, the merge of the gathered shards): likewise, held to _lib.EVAL_SHARD_SIGNATURES. */
 #include "fmmt_eval_shard.h"
+/* The MELD training ColorJitter inside the uint8 pre-step (fmmt_patch_embed_u8_jitter / _jitter_ln_fwd, fmmt_jitter_table_check): likewise, held to _lib.JITTER_SIGNATURES. */
+#include "fmmt_jitter.h"
 
 #ifdef __cplusplus
 }
