@@ -151,6 +151,17 @@ JITTER_SIGNATURES = {
 JITTER_WORDS, JITTER_BANDS = 8, 56
 JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE, JITTER_NONE = 0, 1, 2, 3, 4
 
+# include/fmmt_aug.h, one to one: a tenth table and header -- the uint8 pre-step pair with the Aff-Wild2 chain's per-frame record, the byte workspace
+# of the frame behind `partial` and the host check of a record (tests/test_aff_augment_cpu.py holds table, header and library together)
+AUG_SIGNATURES = {
+    "fmmt_aug_table_check": (_i, [_p, _i]),
+    "fmmt_aug_workspace_bytes": (C.c_size_t, [_i]),
+    "fmmt_patch_embed_u8_aug": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, C.c_size_t, _p, _p]),
+    "fmmt_patch_embed_u8_aug_ln_fwd": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _p, C.c_size_t, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p]),
+}
+# the record layout (include/fmmt_aug.h FMMT_AUG_*): words 0-7 a jitter record, 8 flags, 9-11 blur r / ww / fw, 12-15 top / left / h / w, 16-17 noise key
+AUG_WORDS, AUG_FLAG_GRAY, AUG_MAX_RADIUS, AUG_HALO = 20, 1, 1, 6
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -171,7 +182,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

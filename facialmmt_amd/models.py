@@ -60,9 +60,12 @@ class SwinForAffwildClassification(nn.Module):
         self.classifier = nn.Linear(64, args.num_labels)
         self.tau = args.tau
 
-    def forward(self, images_feature=None, is_trg_task=None, labels=None, criterion=None, n_valid=None, jitter=None):
-        """jitter (None: no augmentation): augment.ColorJitter's table for uint8 images_feature -- the MELD train transform; the auxiliary task never passes one"""
+    def forward(self, images_feature=None, is_trg_task=None, labels=None, criterion=None, n_valid=None, jitter=None, augment=None):
+        """jitter (None: no augmentation): augment.ColorJitter's table for uint8 images_feature -- the MELD train transform; the auxiliary task never passes one.
+        augment (None: no augmentation): augment.AffWildAugment's table for uint8 images_feature -- the Aff-Wild2 train transform of the auxiliary task"""
         kw = {} if jitter is None else {"jitter": jitter}
+        if augment is not None:
+            kw["augment"] = augment
         feats = self.swin(images_feature, **kw) if n_valid is None else self.swin(images_feature, n_valid=n_valid, **kw)
         logits = self.classifier(self.nonlinear(self.linear(feats.to(self.linear.weight.dtype))))
         if is_trg_task:

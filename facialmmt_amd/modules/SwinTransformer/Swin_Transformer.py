@@ -317,19 +317,22 @@ class PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
         self.norm = norm_layer(embed_dim) if norm_layer is not None else None
 
-    def forward_u8(self, x, resize="pil", dtype=None, jitter=None):
+    def forward_u8(self, x, resize="pil", dtype=None, jitter=None, augment=None):
         """x: (B, S, S, 3) uint8 face crops in image layout.  The reference's host-side pre-step -- bicubic resize to
         224x224, ToTensor, Normalize(.5,.5) (utils/util.py:43-52 'pil' / utils/dataset.py:47-69 'cv2') -- is fused into the
         patch gather (ops.patch_embed_u8): same result as forward(Normalize(ToTensor(resize(x)))), without the float image.
-        jitter: a (B, 8) table of augment.ColorJitter -- the MELD train transform (utils/dataset.py:35-39,62-63) between the resize and ToTensor."""
+        jitter: a (B, 8) table of augment.ColorJitter -- the MELD train transform (utils/dataset.py:35-39,62-63) between the resize and ToTensor.
+        augment: a (B, 20) table of augment.AffWildAugment -- the Aff-Wild2 train transform (utils/util.py:22-60): grayscale / jitter / blur between
+        the resize and ToTensor, RandomErasing behind Normalize.  Not both (ValueError)."""
         _require(tuple(self.img_size) == (224, 224) and tuple(self.patch_size) == (4, 4) and self.in_chans == 3,
                  "PatchEmbed kernel is built for 3x224x224 images and 4x4 patches")
         B = x.shape[0]
         w2d = self.proj.weight.view(self.embed_dim, -1)
         dt = dtype or self.proj.weight.dtype
+        kw = {} if augment is None else {"augment": augment}
         if ops.patch_embed_u8_ln_fusable(x, w2d, self.norm, dt):   # pre-step, projection, bias and LayerNorm: one launch
-            return ops.patch_embed_u8_ln(x, resize, w2d, self.proj.bias, self.norm.weight, self.norm.bias, self.norm.eps, dt, jitter=jitter).view(B, self.num_patches, self.embed_dim)
-        cols = ops.patch_embed_u8(x, resize, dt, jitter=jitter)
+            return ops.patch_embed_u8_ln(x, resize, w2d, self.proj.bias, self.norm.weight, self.norm.bias, self.norm.eps, dt, jitter=jitter, **kw).view(B, self.num_patches, self.embed_dim)
+        cols = ops.patch_embed_u8(x, resize, dt, jitter=jitter, **kw)
         if ops.patch_proj_ln_fusable(cols, w2d, self.norm):    # projection + bias + LayerNorm: one launch
             return ops.patch_proj_ln(cols, w2d, self.proj.bias, self.norm.weight, self.norm.bias, self.norm.eps).view(B, self.num_patches, self.embed_dim)
         y = ops.linear(cols, w2d, self.proj.bias).view(B, self.num_patches, self.embed_dim)
@@ -441,12 +444,17 @@ class SwinTransformer(nn.Module):
     input_resize = "pil"
     input_dtype = None
 
-    def forward_features(self, x, n_valid=None, jitter=None):
+    def forward_features(self, x, n_valid=None, jitter=None, augment=None):
         _require(self.pos_drop.p == 0.0 or not self.training, "pos_drop p > 0 in training")
+        if jitter is not None and augment is not None:
+            raise ValueError("jitter= (the MELD transform) and augment= (the Aff-Wild2 chain, with a jitter record of its own) exclude each other")
         if x.dtype == torch.uint8:
-            x = self.patch_embed.forward_u8(x, self.input_resize, self.input_dtype, jitter=jitter)
+            kw = {} if augment is None else {"augment": augment}           # handed down only when set
+            x = self.patch_embed.forward_u8(x, self.input_resize, self.input_dtype, jitter=jitter, **kw)
         elif jitter is not None:
             raise ValueError(f"a ColorJitter table needs uint8 frames (it works on the resize's bytes), got {x.dtype}")
+        elif augment is not None:
+            raise ValueError(f"an AffWildAugment table needs uint8 frames (it works on the resize's bytes), got {x.dtype}")
         else:
             x = self.patch_embed(x)
         self._draw_drop_paths(x.shape[0], x.device)
@@ -454,12 +462,16 @@ class SwinTransformer(nn.Module):
             x = layer(x)
         return self._head(x, n_valid)
 
-    def forward(self, x, n_valid=None, jitter=None):
+    def forward(self, x, n_valid=None, jitter=None, augment=None):
         """n_valid (1-element int32 device tensor; None: the reference's forward): x holds a fixed capacity of frames, the first n_valid real --
         the head's BatchNorm then runs over those rows (one real frame: what the duplication below computes, by its arithmetic).
-        jitter (None: no augmentation): augment.ColorJitter's table, one record per frame of x (uint8 frames only)"""
+        jitter (None: no augmentation): augment.ColorJitter's table, one record per frame of x (uint8 frames only)
+        augment (None: no augmentation): augment.AffWildAugment's table, likewise; not together with jitter"""
+        kw = {} if augment is None else {"augment": augment}
         if n_valid is not None:
-            return self.forward_features(x, n_valid, jitter)
+            return self.forward_features(x, n_valid, jitter, **kw)
         if len(x) == 1:                              # BatchNorm needs two samples (ref :535-538)
-            return self.forward_features(torch.cat((x, x), dim=0), jitter=None if jitter is None else torch.cat((jitter, jitter), dim=0))[:1]
-        return self.forward_features(x, jitter=jitter)
+            if augment is not None:
+                kw = {"augment": torch.cat((augment, augment), dim=0)}
+            return self.forward_features(torch.cat((x, x), dim=0), jitter=None if jitter is None else torch.cat((jitter, jitter), dim=0), **kw)[:1]
+        return self.forward_features(x, jitter=jitter, **kw)

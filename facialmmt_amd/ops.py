@@ -1627,18 +1627,45 @@ def _jitter_table(jitter, img_u8, what):
     return jitter.contiguous()
 
 
-def patch_embed_u8(img_u8: torch.Tensor, mode: str, dtype, jitter=None) -> torch.Tensor:
+def _augment_table(augment, jitter, img_u8, what):
+    """the (n, 20) int32 device table of augment.AffWildAugment (include/fmmt_aug.h), checked against the frames it is for; not with a jitter table"""
+    if jitter is not None:
+        raise ValueError(f"{what}: jitter= (the MELD transform) and augment= (the Aff-Wild2 chain, which holds a jitter record of its own) exclude each other")
+    if not torch.is_tensor(augment) or augment.dtype != torch.int32 or tuple(augment.shape) != (img_u8.shape[0], _lib.AUG_WORDS):
+        got = f"{tuple(augment.shape)} {augment.dtype}" if torch.is_tensor(augment) else type(augment).__name__
+        raise ValueError(f"{what}: the AffWildAugment table is ({img_u8.shape[0]}, {_lib.AUG_WORDS}) int32, one record per frame, got {got}")
+    if augment.device != img_u8.device:
+        raise ValueError(f"{what}: the AffWildAugment table is on {augment.device}, the frames on {img_u8.device}")
+    return augment.contiguous()
+
+
+def _augment_scratch(n, device):
+    """the contrast statistic's words and the byte image of the frames (fmmt_aug_workspace_bytes: n x 224 x 224 x 3) a call writes, then reads"""
+    return (torch.empty((n, _lib.JITTER_BANDS), dtype=torch.int32, device=device), torch.empty((n, 224, 224, 3), dtype=torch.uint8, device=device))
+
+
+def patch_embed_u8(img_u8: torch.Tensor, mode: str, dtype, jitter=None, augment=None) -> torch.Tensor:
     """(n, S, S, 3) uint8 crops (image layout) -> (n*3136, 48) patch matrix of Normalize(ToTensor(resize_224(img))):
     the input pre-step fused into PatchEmbed's gather (no gradient: the input is integer data).
     jitter: None, or the (n, 8) int32 table of augment.ColorJitter -- the frame's brightness / contrast / saturation / hue operations on the resized
-    bytes, in front of ToTensor (fmmt_patch_embed_u8_jitter: two launches; None is the call above, through the entry point above)."""
+    bytes, in front of ToTensor (fmmt_patch_embed_u8_jitter: two launches; None is the call above, through the entry point above).
+    augment: None, or the (n, 20) int32 table of augment.AffWildAugment -- the Aff-Wild2 chain grayscale / jitter / Gaussian blur on the resized
+    bytes and RandomErasing's noise rectangle behind the Normalize table (fmmt_patch_embed_u8_aug: three launches); not together with jitter."""
     _need_cuda(img_u8, "patch_embed_u8")
     if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != img_u8.shape[2] or img_u8.shape[3] != 3:
         raise ValueError(f"patch_embed_u8 expects (n, S, S, 3) uint8 crops, got {tuple(img_u8.shape)} {img_u8.dtype}")
+    if augment is not None:
+        augment = _augment_table(augment, jitter, img_u8, "patch_embed_u8")
     img_u8 = img_u8.contiguous()
     n, S = img_u8.shape[0], img_u8.shape[1]
     code, tab, lut = resize_tables(mode, S, img_u8.device)
     cols = torch.empty((n * 3136, 48), dtype=dtype, device=img_u8.device)
+    if augment is not None:
+        partial, ws = _augment_scratch(n, img_u8.device)
+        rc = _lib.load().fmmt_patch_embed_u8_aug(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(augment), _p(partial), _p(ws), ws.numel(),
+                                                 _p(cols), _st())
+        check(rc, f"fmmt_patch_embed_u8_aug(n={n},S={S},{mode})")
+        return cols
     if jitter is not None:
         jitter = _jitter_table(jitter, img_u8, "patch_embed_u8")
         partial = torch.empty((n, _lib.JITTER_BANDS), dtype=torch.int32, device=img_u8.device)
@@ -1660,10 +1687,12 @@ class PatchEmbedU8LnFn(Function):
     backward = PatchProjLnFn's (the input is integer data: no input gradient)."""
 
     @staticmethod
-    def forward(ctx, img_u8, mode, weight, bias, gamma, beta, eps, dtype, grad_on=True, jitter=None):
+    def forward(ctx, img_u8, mode, weight, bias, gamma, beta, eps, dtype, grad_on=True, jitter=None, augment=None):
         _need_cuda(img_u8, "patch_embed_u8_ln")
         if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[1] != img_u8.shape[2] or img_u8.shape[3] != 3:
             raise ValueError(f"patch_embed_u8 expects (n, S, S, 3) uint8 crops, got {tuple(img_u8.shape)} {img_u8.dtype}")
+        if augment is not None:
+            augment = _augment_table(augment, jitter, img_u8, "patch_embed_u8_ln")
         img_u8 = img_u8.contiguous()
         n, S = img_u8.shape[0], img_u8.shape[1]
         code, tab, lut = resize_tables(mode, S, img_u8.device)
@@ -1677,7 +1706,13 @@ class PatchEmbedU8LnFn(Function):
         mean = torch.empty(M, dtype=torch.float32, device=dev) if train else None
         rstd = torch.empty(M, dtype=torch.float32, device=dev) if train else None
         bias32 = bias.detach().float().contiguous() if bias is not None else None
-        if jitter is not None:           # augment.ColorJitter's table: the same launch behind the contrast statistic's (fmmt_patch_embed_u8_jitter_ln_fwd)
+        if augment is not None:          # augment.AffWildAugment's table: statistic, pixels into the byte workspace, then this launch's finish (fmmt_patch_embed_u8_aug_ln_fwd)
+            partial, ws = _augment_scratch(n, dev)
+            rc = _lib.load().fmmt_patch_embed_u8_aug_ln_fwd(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(augment), _p(partial), _p(ws),
+                                                            ws.numel(), _p(_lp(weight, dtype)), _p(bias32), _p(g), _p(b), float(eps),
+                                                            _p(cols), _p(x_pre), _p(y), _p(mean), _p(rstd), _st())
+            check(rc, f"fmmt_patch_embed_u8_aug_ln_fwd(n={n},S={S},{mode})")
+        elif jitter is not None:         # augment.ColorJitter's table: the same launch behind the contrast statistic's (fmmt_patch_embed_u8_jitter_ln_fwd)
             jitter = _jitter_table(jitter, img_u8, "patch_embed_u8_ln")
             partial = torch.empty((n, _lib.JITTER_BANDS), dtype=torch.int32, device=dev)
             rc = _lib.load().fmmt_patch_embed_u8_jitter_ln_fwd(dtype_code(dtype), code, n, S, _p(img_u8), _p(tab), _p(lut), _p(jitter), _p(partial),
@@ -1707,7 +1742,7 @@ class PatchEmbedU8LnFn(Function):
         check(lib.fmmt_layernorm_bwd(dtype_code(dy.dtype), M, C, _p(dy), _p(x_pre), _p(mean), _p(rstd), _p(g), None, _p(dxp), _p(dg), _p(db), 0,
                                      _p(ws), nbytes, _st()), f"fmmt_layernorm_bwd(patch embed, M={M})")
         dw, dbias = wgrad_raw(dxp, cols, ctx.has_bias)
-        return None, None, dw.view_as(weight), dbias, dg, db, None, None, None, None
+        return None, None, dw.view_as(weight), dbias, dg, db, None, None, None, None, None
 
 
 def patch_embed_u8_ln_fusable(img_u8, weight, norm, dtype):
@@ -1716,8 +1751,8 @@ def patch_embed_u8_ln_fusable(img_u8, weight, norm, dtype):
             and not any(t.data_ptr() % 16 for t in (weight, norm.weight, norm.bias)))
 
 
-def patch_embed_u8_ln(img_u8, mode, weight, bias, gamma, beta, eps, dtype, jitter=None):
-    return PatchEmbedU8LnFn.apply(img_u8, mode, weight, bias, gamma, beta, eps, dtype, torch.is_grad_enabled(), jitter)
+def patch_embed_u8_ln(img_u8, mode, weight, bias, gamma, beta, eps, dtype, jitter=None, augment=None):
+    return PatchEmbedU8LnFn.apply(img_u8, mode, weight, bias, gamma, beta, eps, dtype, torch.is_grad_enabled(), jitter, augment)
 
 
 def batch_norm_1d_fwd_raw(x, g, b, running_mean, running_var, momentum, eps, training):

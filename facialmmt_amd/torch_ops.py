@@ -13,6 +13,7 @@ Registered (forward ops return what their backward needs as extra outputs, as cu
     fmmt::window_attention(qkv, table, index, n_img, H, W, heads, shift, scale) -> (out, lse)   W-MSA / SW-MSA core on token-order qkv
     fmmt::patch_embed_u8(img_u8, flavour, bf16) -> cols                                    input pre-step + patch gather (no gradient)
     fmmt::patch_embed_u8_jitter(img_u8, flavour, bf16, jitter) -> cols                     the same with augment.ColorJitter's per-frame table applied to the resized bytes
+    fmmt::patch_embed_u8_aug(img_u8, flavour, bf16, augment) -> cols                       the same with augment.AffWildAugment's per-frame table: grayscale / jitter / blur / erase
     fmmt::layer_norm_merge(x, gamma, beta, eps, merge_hw) -> (y, mean, rstd)              PatchMerging's 2x2 gather + LayerNorm(4C)
     fmmt::linear_splitk(x, weight, bias?) -> y                                            the 37632 -> 512 embedding head (split-K launch)
     fmmt::batch_norm_1d(x, gamma, beta, running_mean, running_var, momentum, eps, training) -> (y, save_mean, save_invstd, running_mean', running_var')
@@ -270,6 +271,16 @@ def patch_embed_u8_jitter(img_u8: Tensor, flavour: str, bf16: bool, jitter: Tens
 
 @patch_embed_u8_jitter.register_fake
 def _(img_u8, flavour, bf16, jitter):
+    return img_u8.new_empty(img_u8.shape[0] * 3136, 48, dtype=torch.bfloat16 if bf16 else torch.float32)
+
+
+@torch.library.custom_op(f"{_LIB}::patch_embed_u8_aug", mutates_args=(), device_types="cuda")
+def patch_embed_u8_aug(img_u8: Tensor, flavour: str, bf16: bool, augment: Tensor) -> Tensor:
+    return ops.patch_embed_u8(img_u8, flavour, torch.bfloat16 if bf16 else torch.float32, augment=augment)
+
+
+@patch_embed_u8_aug.register_fake
+def _(img_u8, flavour, bf16, augment):
     return img_u8.new_empty(img_u8.shape[0] * 3136, 48, dtype=torch.bfloat16 if bf16 else torch.float32)
 
 

@@ -310,6 +310,18 @@ def _need_u8_frames(frames):
         raise ValueError(f"color_jitter works on the uint8 crops the pre-step resizes (frames (.., S, S, 3) uint8), got {frames.dtype} frames")
 
 
+def _check_augment(augment):
+    from .augment import AffWildAugment
+    if augment is not None and not isinstance(augment, AffWildAugment):
+        raise TypeError(f"augment: an augment.AffWildAugment or None, got {type(augment).__name__}")
+    return augment
+
+
+def _need_u8_images(images):
+    if images.dtype != torch.uint8:
+        raise ValueError(f"augment works on the uint8 crops the pre-step resizes (images (B, S, S, 3) uint8), got {images.dtype} images")
+
+
 class TargetStep(StepState):
     """Swin (train mode, Gumbel-softmax head) -> frame filter -> multimodal model -> CE -> backward ->
     (every `accumulation_steps`) clip + AdamW + schedule, as train.py:46-143.  Only the multimodal
@@ -2062,17 +2074,27 @@ class GraphedAuxStep(StepState):
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "aux", ("swin",), "aux_accumulation_steps"
 
     def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, augment=None):
         """`pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
         pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
         device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
         (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
         Under an active averager `__call__(images, labels, global_rows=...)` weights the differentiated loss with row_weight (ROW_WEIGHT_NOTE at
         GraphedTargetStep): ranks that hold different numbers of real rows then step on the mean over all real rows.
-        `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too."""
+        `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too.
+        `augment` (an augment.AffWildAugment; None: no augmentation, the launches of before): the Aff-Wild2 train transform (utils/util.py:22-60)
+        inside the uint8 pre-step.  The draw of the per-image table is PART of graph A, in front of Swin's forward: every replay augments anew and a
+        resumed generator walks the same tables (nothing is added to state_dict()).  With pad_rows the padded zero images get records too; their
+        rows stay out of BatchNorm and the loss.  `last_augment`: the table of the last replay (device, int32 (B, 20), a view of the static buffer
+        the captured draw writes).  Images must be uint8 (ValueError, here and at the call)."""
         from . import ops
         from .parallel import GradientAverager
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
+        self.augment, self.last_augment = _check_augment(augment), None
+        if self.augment is not None:
+            _need_u8_images(images)
+            from ._lib import AUG_WORDS
+            self.last_augment = torch.zeros((images.shape[0], AUG_WORDS), dtype=torch.int32, device=images.device)   # static: graph A's draw lands here
         self.static = [images.clone(), labels.clone()]
         self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
         self.n_valid = torch.full((1,), images.shape[0], dtype=torch.int32, device=images.device) if self.pad_rows else None
@@ -2105,10 +2127,14 @@ class GraphedAuxStep(StepState):
         if self.shadows is not None:
             self.shadows.refresh()
         images, labels = self.static
+        kw = {}
+        if self.augment is not None:                         # one record per image of the captured batch, drawn just ahead of Swin
+            self.last_augment.copy_(self.augment.draw(images.shape[0], images.device))
+            kw["augment"] = self.last_augment
         if self.pad_rows:
-            loss = self.swin(images, False, labels, F.cross_entropy, n_valid=self.n_valid) / self.args.aux_accumulation_steps
+            loss = self.swin(images, False, labels, F.cross_entropy, n_valid=self.n_valid, **kw) / self.args.aux_accumulation_steps
         else:
-            loss = self.swin(images, False, labels, F.cross_entropy) / self.args.aux_accumulation_steps
+            loss = self.swin(images, False, labels, F.cross_entropy, **kw) / self.args.aux_accumulation_steps
         (loss if self.row_weight is None else loss * self.row_weight).backward()
         self.tail.hand_over()
         if self.monitor is not None:
@@ -2117,6 +2143,8 @@ class GraphedAuxStep(StepState):
 
     def __call__(self, images, labels, global_rows=None):
         """`global_rows`: GraphedTargetStep.__call__'s -- the real rows all ranks hold in this micro-step; pad_rows under an active exchange only"""
+        if self.augment is not None:
+            _need_u8_images(images)                          # ValueError before anything is copied or launched
         rows = b = self.static[0].shape[0]
         padding = self.pad_rows and images.dim() == self.static[0].dim() and images.shape[0] != rows
         if padding:
@@ -2151,12 +2179,19 @@ class AuxStep(StepState):
     `aux_accumulation_steps`.  BASELINE.json configs[4] alternates these steps with target steps per epoch."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = GraphedAuxStep.STATE_KIND, GraphedAuxStep.STATE_MODELS, GraphedAuxStep.STATE_WINDOW
 
-    def __init__(self, swin_model, optimizer, scheduler, args):
+    def __init__(self, swin_model, optimizer, scheduler, args, augment=None):
+        """`augment` (an augment.AffWildAugment; None: no augmentation): the Aff-Wild2 train transform (utils/util.py:22-60) on the uint8 images,
+        inside the pre-step -- every call draws a table from the device generator, one record per image, and keeps it in `last_augment`."""
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
         self.i_batch = 0
+        self.augment, self.last_augment = _check_augment(augment), None
 
     def __call__(self, images, labels):
-        loss = self.swin(images, False, labels, F.cross_entropy) / self.args.aux_accumulation_steps
+        kw = {}
+        if self.augment is not None:
+            _need_u8_images(images)                          # ValueError before anything is launched
+            self.last_augment = kw["augment"] = self.augment.draw(images.shape[0], images.device)
+        loss = self.swin(images, False, labels, F.cross_entropy, **kw) / self.args.aux_accumulation_steps
         loss.backward()
         self.i_batch += 1
         if self.i_batch % self.args.aux_accumulation_steps == 0:

@@ -453,7 +453,8 @@ int fmmt_adamw_batch(int n_desc, int n_blocks, const void* desc, const float* lr
  *   MELD:      cv2.resize(im, (224,224), INTER_CUBIC) on the uint8 array -> ToTensor -> Normalize  utils/dataset.py:47-69
  * followed by PatchEmbed's 4x4 / stride-4 patch gather (Swin_Transformer.py:407,419): the output IS the
  * (n*3136, 48) operand of the patch-embedding GEMM (same layout as fmmt_patch_im2col), element type `dtype`.
- * Augmentations (ColorJitter, RandomErasing, ...) are host-side data pipeline and not part of this entry point.
+ * Augmentations are not part of this entry point: the training transforms run on the device behind entry points of their own, on a per-frame
+ * table of draws (fmmt_jitter.h: the MELD ColorJitter; fmmt_aug.h: the Aff-Wild2 grayscale / ColorJitter / blur / RandomErasing chain).
  *
  * fmmt_resize_table   HOST function: fills table[out_size][8] = {4 source indices, 4 integer weights} per output
  *                     coordinate (the same table serves x and y) and lut[256] = float32 Normalize(ToTensor(byte)), with the
@@ -528,6 +529,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_eval_shard.h"
 /* The MELD training ColorJitter inside the uint8 pre-step (fmmt_patch_embed_u8_jitter / _jitter_ln_fwd, fmmt_jitter_table_check): likewise, held to _lib.JITTER_SIGNATURES. */
 #include "fmmt_jitter.h"
+/* The Aff-Wild2 training augmentation of the auxiliary task inside the uint8 pre-step (grayscale, ColorJitter, Gaussian blur, RandomErasing): likewise, held to _lib.AUG_SIGNATURES. */
+#include "fmmt_aug.h"
 
 #ifdef __cplusplus
 }
