@@ -39,6 +39,13 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _seed_args(seed):
+    """a dropout seed as the entry points take it, (seed_i, seed_t): a python int, or a 1-element int64 CUDA tensor the kernel reads at run time
+    (graph-replay safe) with 0 in the integer's place"""
+    seed_t = seed if isinstance(seed, torch.Tensor) else None
+    return (0 if seed_t is not None else int(seed)), seed_t
+
+
 # ------------------------------------------------------------------------------------------------
 # raw launch helpers (no autograd)
 # ------------------------------------------------------------------------------------------------
@@ -358,6 +365,13 @@ def adamw_batch_guarded(n, blocks, desc, lr, step, total_norm, beta1, beta2, eps
                                                float(weight_decay), float(max_norm), 1 if hf else 0, _st()), "fmmt_adamw_batch_guarded")
 
 
+def grad_handover_raw(n, blocks, table, partial, norm_out):
+    """fmmt_grad_handover over a device table of `n` records (train_step.FusedHandOver's layout; `blocks` blocks of 4096 elements, one fp32 word
+    of `partial` each): every gradient into its fp32 slot and the norm of all of them into `norm_out`, on the current stream of the table's device"""
+    check(_lib.load().fmmt_grad_handover(n, blocks, _p(table), _p(partial), _p(norm_out), torch.cuda.current_stream(table.device).cuda_stream),
+          f"fmmt_grad_handover(n={n},blocks={blocks})")
+
+
 def _guard_words(words):
     if words.dtype != torch.int64 or not words.is_contiguous() or words.numel() != _lib.GUARD_WORDS:
         raise ValueError(f"words: a contiguous int64 tensor of {_lib.GUARD_WORDS} entries (include/fmmt_guard.h)")
@@ -492,8 +506,7 @@ class PlmFfnFn(torch.autograd.Function):
         h = torch.nn.functional.linear(act, w2, b2)
         C = h.shape[-1]
         x2 = _c16(x.reshape(-1, C))
-        seed_t = seed if isinstance(seed, torch.Tensor) else None
-        seed_i = 0 if seed_t is not None else int(seed)
+        seed_i, seed_t = _seed_args(seed)
         xsum, y = plm_tail_fwd_raw(h.reshape(-1, C), x2, gamma.detach(), beta.detach(), eps, p, seed_i, seed_t, salt)
         ctx.save_for_backward(x2, w1, w2, pre, act, xsum, gamma, seed_t)
         ctx.cfg = (float(eps), float(p), seed_i, int(salt))
@@ -525,13 +538,8 @@ class PlmSublayerTailFn(torch.autograd.Function):
     def forward(ctx, x, res, weight, bias, gamma, beta, eps, p, seed, salt):
         h = torch.nn.functional.linear(x, weight, bias)
         C = h.shape[-1]
-        h2, r2 = h.reshape(-1, C), _c16(res.reshape(-1, C))
-        M = h2.shape[0]
-        xsum, y = torch.empty_like(h2), torch.empty_like(h2)
-        seed_t = seed if isinstance(seed, torch.Tensor) else None
-        seed_i = 0 if seed_t is not None else int(seed)
-        check(_lib.load().fmmt_plm_dropadd_ln_fwd(M, C, float(eps), _p(h2), _p(r2), _p(gamma.detach()), _p(beta.detach()), float(p), seed_i, _p(seed_t),
-                                                  int(salt), _p(xsum), _p(y), _st()), f"fmmt_plm_dropadd_ln_fwd(M={M},C={C})")
+        seed_i, seed_t = _seed_args(seed)
+        xsum, y = plm_tail_fwd_raw(h.reshape(-1, C), _c16(res.reshape(-1, C)), gamma.detach(), beta.detach(), eps, p, seed_i, seed_t, salt)
         ctx.save_for_backward(x, weight, xsum, gamma, seed_t)
         ctx.cfg = (float(eps), float(p), seed_i, int(salt))
         return y.reshape(h.shape)
@@ -541,14 +549,7 @@ class PlmSublayerTailFn(torch.autograd.Function):
         x, weight, xsum, gamma, seed_t = ctx.saved_tensors
         eps, p, seed_i, salt = ctx.cfg
         M, C = xsum.shape
-        dy2 = _c16(dy.reshape(M, C))
-        lib = _lib.load()
-        dx, dh = torch.empty_like(xsum), torch.empty_like(xsum)
-        dgamma, dbeta, dbias = torch.empty_like(gamma), torch.empty_like(gamma), torch.empty_like(gamma)
-        nbytes = lib.fmmt_plm_dropadd_ln_bwd_workspace(M, C)
-        ws = _ws(nbytes, xsum.device)
-        check(lib.fmmt_plm_dropadd_ln_bwd(M, C, eps, _p(dy2), _p(xsum), _p(gamma.detach()), p, seed_i, _p(seed_t), salt, _p(dx), _p(dh), _p(dgamma), _p(dbeta),
-                                          _p(dbias), _p(ws), nbytes, _st()), f"fmmt_plm_dropadd_ln_bwd(M={M},C={C})")
+        dx, dh, dgamma, dbeta, dbias = plm_tail_bwd_raw(_c16(dy.reshape(M, C)), xsum, gamma.detach(), eps, p, seed_i, seed_t, salt)
         dxin = dh.reshape(dy.shape).matmul(weight) if ctx.needs_input_grad[0] else None
         dw = dh.t().mm(x.reshape(-1, x.shape[-1])) if ctx.needs_input_grad[2] else None
         return dxin, dx.reshape(dy.shape), dw, dbias, dgamma, dbeta, None, None, None, None
@@ -569,8 +570,7 @@ class DropAddLnFn(Function):
         g, b = _c16(gamma.detach()), _c16(beta.detach())
         assert h2.dtype == torch.bfloat16 and r2.dtype == torch.bfloat16 and g.dtype == b.dtype and g.dtype in (torch.float32, torch.bfloat16)
         xsum, y = torch.empty_like(h2), torch.empty_like(h2)
-        seed_t = seed if isinstance(seed, torch.Tensor) else None
-        seed_i = 0 if seed_t is not None else int(seed)
+        seed_i, seed_t = _seed_args(seed)
         check(_lib.load().fmmt_dropadd_ln_fwd(dtype_code(g.dtype), M, C, float(eps), _p(h2), _p(r2), _p(g), _p(b), float(p), seed_i, _p(seed_t), int(salt),
                                               _p(xsum), _p(y), _st()), f"fmmt_dropadd_ln_fwd(M={M},C={C})")
         ctx.save_for_backward(xsum, g, seed_t)
@@ -634,8 +634,7 @@ class PlmSelfAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, wq, wk, wv, bq, bk, bv, w_all, b_all, num_heads, scale, p, seed, key_bias):
         qkv = torch.nn.functional.linear(x, w_all, b_all)
-        seed_t = seed if isinstance(seed, torch.Tensor) else None
-        seed_i = 0 if seed_t is not None else int(seed)
+        seed_i, seed_t = _seed_args(seed)
         if key_bias is not None:                                 # the kernels read it as a row-major fp32 (B, S) array
             key_bias = key_bias.detach().to(torch.float32).contiguous()
             assert key_bias.shape == x.shape[:2], f"key_bias must be (B, S) = {tuple(x.shape[:2])}, got {tuple(key_bias.shape)}"
@@ -830,14 +829,7 @@ class MlpLnFn(Function):
         dw2, db2 = wgrad_raw(dy2, h, True, rowscale, ctx.rps)
         dw1, db1 = wgrad_raw(dh, xn, True)
         del dh
-        dx = torch.empty_like(x2)
-        dg = torch.empty(C, dtype=torch.float32, device=x2.device)
-        db = torch.empty(C, dtype=torch.float32, device=x2.device)
-        nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-        ws = _ws(nbytes, x2.device)
-        rc = lib.fmmt_layernorm_bwd(dtype_code(x2.dtype), x2.shape[0], C, _p(dxn), _p(x2), _p(mean), _p(rstd), _p(g), _p(dy2), _p(dx), _p(dg), _p(db), 0,
-                                    _p(ws), nbytes, _st())
-        check(rc, "fmmt_layernorm_bwd(mlp_ln)")
+        dx, dg, db = layernorm_bwd_raw(dxn, x2, mean, rstd, g, add=dy2)
         return dx.reshape(ctx.xshape), dg, db, None, dw1, db1, dw2, db2, None, None, None
 
 
@@ -859,46 +851,57 @@ def mlp(x, w1, b1, w2, b2, res=None, rowscale=None, rows_per_scale=1):
 # ------------------------------------------------------------------------------------------------
 # LayerNorm (optionally with the PatchMerging 2x2 gather folded in)
 # ------------------------------------------------------------------------------------------------
+def layernorm_fwd_raw(x, g, b, eps, merge_hw=0):
+    """fmmt_layernorm_fwd over the last dimension of a contiguous x, g / b fp32: returns (y, mean, rstd).  merge_hw: x is a (n, merge_hw^2, C/4)
+    token grid and a row of the LayerNorm is PatchMerging's 2x2-neighbour concat -> y (n, merge_hw^2 / 4, C) (Swin_Transformer.py:316-325)"""
+    if merge_hw:
+        n, L, Cq = x.shape
+        assert L == merge_hw * merge_hw
+        M, C = n * (merge_hw // 2) ** 2, 4 * Cq
+        out_shape = (n, (merge_hw // 2) ** 2, C)
+    else:
+        C = x.shape[-1]
+        M = x.numel() // C
+        out_shape = x.shape
+    y = torch.empty(out_shape, dtype=x.dtype, device=x.device)
+    mean = torch.empty(M, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    rc = _lib.load().fmmt_layernorm_fwd(dtype_code(x.dtype), M, C, _p(x), _p(g), _p(b), float(eps), _p(y), _p(mean), _p(rstd), merge_hw, _st())
+    check(rc, f"fmmt_layernorm_fwd(M={M},C={C},merge={merge_hw})")
+    return y, mean, rstd
+
+
+def layernorm_bwd_raw(dy, x, mean, rstd, g, add=None, merge_hw=0):
+    """fmmt_layernorm_bwd on what layernorm_fwd_raw took and returned (all contiguous): (dx, dgamma, dbeta), the last two fp32.  add: a tensor of
+    x's shape summed into dx (the gradient of the residual branch around a pre-norm LayerNorm)"""
+    M, C = mean.numel(), g.numel()
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    nbytes = lib.fmmt_layernorm_bwd_workspace(C)
+    ws = _ws(nbytes, x.device)
+    rc = lib.fmmt_layernorm_bwd(dtype_code(x.dtype), M, C, _p(dy), _p(x), _p(mean), _p(rstd), _p(g), _p(add), _p(dx), _p(dg), _p(db), merge_hw,
+                                _p(ws), nbytes, _st())
+    check(rc, f"fmmt_layernorm_bwd(M={M},C={C},merge={merge_hw}{',add' if add is not None else ''})")
+    return dx, dg, db
+
+
 class LayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, merge_hw):
         _need_cuda(x, "layer_norm")
-        lib = _lib.load()
         x = x.contiguous()
-        if merge_hw:
-            n, L, Cq = x.shape
-            assert L == merge_hw * merge_hw
-            M, C = n * (merge_hw // 2) ** 2, 4 * Cq
-            out_shape = (n, (merge_hw // 2) ** 2, C)
-        else:
-            C = x.shape[-1]
-            M = x.numel() // C
-            out_shape = x.shape
-        y = torch.empty(out_shape, dtype=x.dtype, device=x.device)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
         g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        rc = lib.fmmt_layernorm_fwd(dtype_code(x.dtype), M, C, _p(x), _p(g), _p(b), eps, _p(y), _p(mean), _p(rstd),
-                                    merge_hw, _st())
-        check(rc, f"fmmt_layernorm_fwd(M={M},C={C},merge={merge_hw})")
+        y, mean, rstd = layernorm_fwd_raw(x, g, b, eps, merge_hw)
         ctx.save_for_backward(x, mean, rstd, g)
-        ctx.dims = (M, C, merge_hw)
+        ctx.merge_hw = merge_hw
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, mean, rstd, g = ctx.saved_tensors
-        M, C, merge_hw = ctx.dims
-        lib = _lib.load()
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        dg = torch.empty(C, dtype=torch.float32, device=x.device)
-        db = torch.empty(C, dtype=torch.float32, device=x.device)
-        nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-        ws = _ws(nbytes, x.device)
-        rc = lib.fmmt_layernorm_bwd(dtype_code(x.dtype), M, C, _p(dy), _p(x), _p(mean), _p(rstd), _p(g), None, _p(dx),
-                                    _p(dg), _p(db), merge_hw, _p(ws), nbytes, _st())
-        check(rc, f"fmmt_layernorm_bwd(M={M},C={C},merge={merge_hw})")
+        dx, dg, db = layernorm_bwd_raw(dy.contiguous(), x, mean, rstd, g, merge_hw=ctx.merge_hw)
         return dx, dg, db, None, None
 
 
@@ -935,18 +938,10 @@ class PatchProjLnFn(Function):
     @staticmethod
     def backward(ctx, dy):
         cols, weight, x_pre, mean, rstd, g = ctx.saved_tensors
-        M, C = x_pre.shape
-        lib = _lib.load()
         dy = dy.contiguous()
-        dxp = torch.empty_like(x_pre)
-        dg = torch.empty(C, dtype=torch.float32, device=dy.device)
-        db = torch.empty(C, dtype=torch.float32, device=dy.device)
-        nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-        ws = _ws(nbytes, dy.device)
-        check(lib.fmmt_layernorm_bwd(dtype_code(dy.dtype), M, C, _p(dy), _p(x_pre), _p(mean), _p(rstd), _p(g), None, _p(dxp), _p(dg), _p(db), 0,
-                                     _p(ws), nbytes, _st()), f"fmmt_layernorm_bwd(patch embed, M={M})")
+        dxp, dg, db = layernorm_bwd_raw(dy, x_pre, mean, rstd, g)
         dw, dbias = wgrad_raw(dxp, cols, ctx.has_bias)
-        dcols = linear_raw(dxp, _lp(weight, dy.dtype, transpose=True), None) if ctx.needs_input_grad[0] else None
+        dcols =linear_raw(dxp, _lp(weight, dy.dtype, transpose=True), None) if ctx.needs_input_grad[0] else None
         return dcols, dw.view_as(weight), dbias, dg, db, None, None
 
 
@@ -968,35 +963,16 @@ class ResidualLayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
         _need_cuda(x, "layer_norm")
-        lib = _lib.load()
         x = x.contiguous()
-        C = x.shape[-1]
-        M = x.numel() // C
-        y = torch.empty_like(x)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
         g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        rc = lib.fmmt_layernorm_fwd(dtype_code(x.dtype), M, C, _p(x), _p(g), _p(b), eps, _p(y), _p(mean), _p(rstd), 0, _st())
-        check(rc, f"fmmt_layernorm_fwd(M={M},C={C})")
+        y, mean, rstd = layernorm_fwd_raw(x, g, b, eps)
         ctx.save_for_backward(x, mean, rstd, g)
-        ctx.dims = (M, C)
         return x.view_as(x), y
 
     @staticmethod
     def backward(ctx, dres, dy):
         x, mean, rstd, g = ctx.saved_tensors
-        M, C = ctx.dims
-        lib = _lib.load()
-        dy = dy.contiguous()
-        add = dres.contiguous() if dres is not None else None
-        dx = torch.empty_like(x)
-        dg = torch.empty(C, dtype=torch.float32, device=x.device)
-        db = torch.empty(C, dtype=torch.float32, device=x.device)
-        nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-        ws = _ws(nbytes, x.device)
-        rc = lib.fmmt_layernorm_bwd(dtype_code(x.dtype), M, C, _p(dy), _p(x), _p(mean), _p(rstd), _p(g), _p(add), _p(dx),
-                                    _p(dg), _p(db), 0, _p(ws), nbytes, _st())
-        check(rc, f"fmmt_layernorm_bwd(M={M},C={C},add)")
+        dx, dg, db = layernorm_bwd_raw(dy.contiguous(), x, mean, rstd, g, add=dres.contiguous() if dres is not None else None)
         return dx, dg, db, None
 
 
@@ -1008,40 +984,49 @@ def residual_layer_norm(x, gamma, beta, eps=1e-5):
 # ------------------------------------------------------------------------------------------------
 # (shifted-)window attention core on token-order qkv
 # ------------------------------------------------------------------------------------------------
+def window_attn_fwd_raw(qkv, tab, index_i32, m, n_img, H, W, num_heads, shift, scale, mask_is_shift):
+    """fmmt_window_attn_fwd on contiguous token-order qkv (n_img*H*W, 3C), the fp32 bias table and the fp32 mask m (nW, 49, 49) or None;
+    mask_is_shift: m is the standard SW-MSA mask of (H, W, shift), which the kernel derives from the window coordinates.  Returns (out, lse)"""
+    C = qkv.shape[-1] // 3
+    nW = (H // 7) * (W // 7)
+    out = torch.empty((n_img * H * W, C), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((n_img * nW * num_heads * 49,), dtype=torch.float32, device=qkv.device)
+    rc = _lib.load().fmmt_window_attn_fwd(dtype_code(qkv.dtype), n_img, H, W, C, num_heads, shift, _p(qkv), _p(tab), _p(index_i32), _p(m),
+                                          m.shape[0] if m is not None else 0, int(mask_is_shift), float(scale), _p(out), _p(lse), _st())
+    check(rc, f"fmmt_window_attn_fwd(n={n_img},H={H},W={W},C={C},heads={num_heads},shift={shift})")
+    return out, lse
+
+
+def window_attn_bwd_raw(qkv, out, dout, lse, tab, index_i32, m, n_img, H, W, num_heads, shift, scale, mask_is_shift):
+    """fmmt_window_attn_bwd on window_attn_fwd_raw's operands and results: returns (dqkv, dtable), dtable fp32 as the table"""
+    C = qkv.shape[-1] // 3
+    lib = _lib.load()
+    dqkv = torch.empty_like(qkv)
+    dtable = torch.empty_like(tab)
+    nbytes = lib.fmmt_window_attn_bwd_workspace(num_heads)
+    ws = _ws(nbytes, qkv.device)
+    rc = lib.fmmt_window_attn_bwd(dtype_code(qkv.dtype), n_img, H, W, C, num_heads, shift, _p(qkv), _p(out), _p(dout), _p(lse), _p(tab), _p(index_i32),
+                                  _p(m), m.shape[0] if m is not None else 0, int(mask_is_shift), float(scale), _p(dqkv), _p(dtable), _p(ws), nbytes, _st())
+    check(rc, f"fmmt_window_attn_bwd(n={n_img},H={H},W={W},C={C},heads={num_heads},shift={shift})")
+    return dqkv, dtable
+
+
 class WindowAttnCoreFn(Function):
     @staticmethod
     def forward(ctx, qkv, table, index_i32, mask, n_img, H, W, num_heads, shift, scale, mask_is_shift):
         _need_cuda(qkv, "window_attention")
-        lib = _lib.load()
         qkv = qkv.contiguous()
-        C = qkv.shape[-1] // 3
-        nW = (H // 7) * (W // 7)
-        out = torch.empty((n_img * H * W, C), dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty((n_img * nW * num_heads * 49,), dtype=torch.float32, device=qkv.device)
         tab = table.detach().float().contiguous()
         m = mask.detach().float().contiguous() if mask is not None else None
-        nWm = m.shape[0] if m is not None else 0
-        rc = lib.fmmt_window_attn_fwd(dtype_code(qkv.dtype), n_img, H, W, C, num_heads, shift, _p(qkv), _p(tab),
-                                      _p(index_i32), _p(m), nWm, int(mask_is_shift), scale, _p(out), _p(lse), _st())
-        check(rc, f"fmmt_window_attn_fwd(n={n_img},H={H},W={W},C={C},heads={num_heads},shift={shift})")
+        ctx.cfg = (n_img, H, W, num_heads, shift, scale, mask_is_shift)
+        out, lse = window_attn_fwd_raw(qkv, tab, index_i32, m, *ctx.cfg)
         ctx.save_for_backward(qkv, out, lse, tab, index_i32, m)
-        ctx.cfg = (n_img, H, W, C, num_heads, shift, scale, nWm, int(mask_is_shift))
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, tab, index_i32, m = ctx.saved_tensors
-        n_img, H, W, C, num_heads, shift, scale, nWm, mis = ctx.cfg
-        lib = _lib.load()
-        dout = dout.contiguous()
-        dqkv = torch.empty_like(qkv)
-        dtable = torch.empty_like(tab)
-        nbytes = lib.fmmt_window_attn_bwd_workspace(num_heads)
-        ws = _ws(nbytes, qkv.device)
-        rc = lib.fmmt_window_attn_bwd(dtype_code(qkv.dtype), n_img, H, W, C, num_heads, shift, _p(qkv), _p(out), _p(dout),
-                                      _p(lse), _p(tab), _p(index_i32), _p(m), nWm, mis, scale, _p(dqkv), _p(dtable),
-                                      _p(ws), nbytes, _st())
-        check(rc, "fmmt_window_attn_bwd")
+        dqkv, dtable = window_attn_bwd_raw(qkv, out, dout.contiguous(), lse, tab, index_i32, m, *ctx.cfg)
         return dqkv, dtable, None, None, None, None, None, None, None, None, None
 
 
@@ -1089,31 +1074,24 @@ def window_block_raw(x2, n_img, H, W, num_heads, shift, ln_g, ln_b, eps, wqkv, b
     attention core, proj Linear as four launches, qkv a temporary (`mask`: the standard SW-MSA mask tensor when shift > 0)."""
     M, C = x2.shape
     dev = x2.device
-    lib = _lib.load()
-    nW = (H // 7) * (W // 7)
-    lse = torch.empty((n_img * nW * num_heads * 49,), dtype=torch.float32, device=dev)
     if C != 96:
-        xn = torch.empty_like(x2)
-        mean = torch.empty(M, dtype=torch.float32, device=dev)
-        rstd = torch.empty(M, dtype=torch.float32, device=dev)
-        check(lib.fmmt_layernorm_fwd(dtype_code(x2.dtype), M, C, _p(x2), _p(ln_g), _p(ln_b), float(eps), _p(xn), _p(mean), _p(rstd), 0, _st()), "fmmt_layernorm_fwd")
+        xn, mean, rstd = layernorm_fwd_raw(x2, ln_g, ln_b, eps)
         qkv = linear_raw(xn, wqkv, bqkv)
-        o = torch.empty_like(x2)
         m = mask.detach().float().contiguous() if mask is not None else None
-        rc = lib.fmmt_window_attn_fwd(dtype_code(x2.dtype), n_img, H, W, C, num_heads, shift, _p(qkv), _p(table), _p(index_i32), _p(m),
-                                      m.shape[0] if m is not None else 0, 1 if m is not None else 0, float(scale), _p(o), _p(lse), _st())
-        check(rc, "fmmt_window_attn_fwd")
+        o, lse = window_attn_fwd_raw(qkv, table, index_i32, m, n_img, H, W, num_heads, shift, scale, m is not None)
         del qkv
         y = linear_raw(o, wproj, bproj, res=x2, rowscale=rowscale, rows_per_scale=H * W)
         return y, xn, o, mean, rstd, lse
+    nW = (H // 7) * (W // 7)
+    lse = torch.empty((n_img * nW * num_heads * 49,), dtype=torch.float32, device=dev)
     y = torch.empty_like(x2)
     xn = torch.empty_like(x2) if save else None
     o = torch.empty_like(x2) if save else None
     mean = torch.empty(M, dtype=torch.float32, device=dev) if save else None
     rstd = torch.empty(M, dtype=torch.float32, device=dev) if save else None
-    rc = lib.fmmt_window_block_fwd(dtype_code(x2.dtype), n_img, H, W, C, num_heads, shift, _p(x2), _p(ln_g), _p(ln_b), float(eps),
-                                   _p(wqkv), _p(bqkv), _p(wproj), _p(bproj), _p(table), _p(index_i32), float(scale), _p(rowscale),
-                                   _p(y), _p(xn), _p(o), _p(mean), _p(rstd), _p(lse), _st())
+    rc = _lib.load().fmmt_window_block_fwd(dtype_code(x2.dtype), n_img, H, W, C, num_heads, shift, _p(x2), _p(ln_g), _p(ln_b), float(eps),
+                                           _p(wqkv), _p(bqkv), _p(wproj), _p(bproj), _p(table), _p(index_i32), float(scale), _p(rowscale),
+                                           _p(y), _p(xn), _p(o), _p(mean), _p(rstd), _p(lse), _st())
     check(rc, f"fmmt_window_block_fwd(n={n_img},H={H},W={W},C={C},heads={num_heads},shift={shift})")
     return y, xn, o, mean, rstd, lse
 
@@ -1155,13 +1133,13 @@ def window_block_backward(dy, x2, xn, o, mean, rstd, lse, g, wqkv, bqkv, wproj, 
     dy2 = dy.reshape(-1, C).contiguous()
     L = H * W
     dwp, dbp = wgrad_raw(dy2, o, True, rowscale, L)             # proj weight gradient (DropPath scale on dy)
-    dqkv = torch.empty((x2.shape[0], 3 * C), dtype=dt, device=x2.device)
-    dtable = torch.empty_like(tab)
-    nbytes = lib.fmmt_window_attn_bwd_workspace(num_heads)
-    ws = _ws(nbytes, x2.device)
     if _WBLOCK_BWD and (dt == torch.bfloat16 or (_WBLOCK_F32 and dt == torch.float32 and C == 96)) and (m is None or shift > 0):
         # (fp32: the same entry point runs the generic restatement of the recompute kernel, csrc/wattn_bwd_ref.hip)
         # attention core backward with q, k, v and d(attention output) re-formed inside the kernel (no qkv / d(out) tensors)
+        dqkv = torch.empty((x2.shape[0], 3 * C), dtype=dt, device=x2.device)
+        dtable = torch.empty_like(tab)
+        nbytes = lib.fmmt_window_attn_bwd_workspace(num_heads)
+        ws = _ws(nbytes, x2.device)
         wql, wpl, bqf = _lp(wqkv, dt), _lp(wproj, dt), (bqkv.detach().float().contiguous() if bqkv is not None else None)
         rc = lib.fmmt_window_block_attn_bwd(dtype_code(dt), n_img, H, W, C, num_heads, shift, _p(xn), _p(dy2), _p(o), _p(lse), _p(wql),
                                             _p(bqf), _p(wpl), _p(tab), _p(index_i32),
@@ -1170,17 +1148,14 @@ def window_block_backward(dy, x2, xn, o, mean, rstd, lse, g, wqkv, bqkv, wproj, 
     else:
         do = linear_raw(dy2, _lp(wproj, dt, transpose=True), None, rowscale=rowscale, rows_per_scale=L)
         qkv = linear_raw(xn, _lp(wqkv, dt), bqkv.detach() if bqkv is not None else None)
-        nWm = m.shape[0] if m is not None else 0
-        rc = lib.fmmt_window_attn_bwd(dtype_code(dt), n_img, H, W, C, num_heads, shift, _p(qkv), _p(o), _p(do), _p(lse), _p(tab), _p(index_i32),
-                                      _p(m), nWm, 1 if m is not None else 0, scale, _p(dqkv), _p(dtable), _p(ws), nbytes, _st())
-        check(rc, "fmmt_window_attn_bwd")
+        dqkv, dtable = window_attn_bwd_raw(qkv, o, do, lse, tab, index_i32, m, n_img, H, W, num_heads, shift, scale, m is not None)
         del qkv, do
-    dx = torch.empty_like(x2)
-    dg = torch.empty(C, dtype=torch.float32, device=x2.device)
-    db = torch.empty(C, dtype=torch.float32, device=x2.device)
     if _WBLOCK_LNBWD and (dt == torch.bfloat16 or (_WBLOCK_F32 and dt == torch.float32)) and C == 96:
         # d(LN out) = dqkv . Wqkv, LayerNorm' and the residual gradient in one launch (fmmt_linear_ln_bwd): d(LN out) is never written
         # (fp32: the generic instantiation of the same kernel, lin_lnbwd_ref_kernel -- what the gradient goldens of the fp32 model check)
+        dx = torch.empty_like(x2)
+        dg = torch.empty(C, dtype=torch.float32, device=x2.device)
+        db = torch.empty(C, dtype=torch.float32, device=x2.device)
         nb2 = lib.fmmt_linear_ln_bwd_workspace(C)
         ws2 = _ws(nb2, x2.device)
         rc = lib.fmmt_linear_ln_bwd(dtype_code(dt), x2.shape[0], C, 3 * C, _p(dqkv), _p(_lp(wqkv, dt, transpose=True)), _p(x2), _p(mean), _p(rstd), _p(g),
@@ -1191,12 +1166,7 @@ def window_block_backward(dy, x2, xn, o, mean, rstd, lse, g, wqkv, bqkv, wproj, 
     dxn = linear_raw(dqkv, _lp(wqkv, dt, transpose=True), None)
     dwq, dbq = wgrad_raw(dqkv, xn, bqkv is not None)
     del dqkv
-    # LayerNorm backward + the residual branch's gradient
-    nb2 = lib.fmmt_layernorm_bwd_workspace(C)
-    ws2 = _ws(nb2, x2.device)
-    rc = lib.fmmt_layernorm_bwd(dtype_code(dt), x2.shape[0], C, _p(dxn), _p(x2), _p(mean), _p(rstd), _p(g), _p(dy2), _p(dx), _p(dg), _p(db), 0,
-                                _p(ws2), nb2, _st())
-    check(rc, "fmmt_layernorm_bwd(window_block)")
+    dx, dg, db = layernorm_bwd_raw(dxn, x2, mean, rstd, g, add=dy2)      # LayerNorm backward + the residual branch's gradient
     return dx.reshape(xshape), dg, db, dwq, dbq, dwp, dbp, dtable
 
 
@@ -1207,68 +1177,87 @@ def window_block(x, ln_w, ln_b, eps, wqkv, bqkv, wproj, bproj, table, index_i32,
 # ------------------------------------------------------------------------------------------------
 # cross-modal multi-head attention core (time-major)
 # ------------------------------------------------------------------------------------------------
-def _mha_ptrs(k, v, E):
-    packed = v is None
-    if packed:
-        return packed, k.shape[0], 2 * E, k.data_ptr(), k.data_ptr() + E * k.element_size()
-    return packed, k.shape[0], E, k.data_ptr(), v.data_ptr()
+def mha_fwd_ptrs(code, Lq, Lk, B, E, num_heads, qp, ldq, kp, vp, ldkv, scale, key_bias, dropout_p, seed_i, seedp, outp, ldo, device, what=""):
+    """THE call of fmmt_mha_fwd, on addresses and row pitches (in elements): `code` the dtype code with its flags, q / k / v / out at qp / kp / vp /
+    outp, key_bias a (B, Lk) fp32 tensor or None, seedp the address of the int64 seed word or None (then seed_i counts).  Returns the new lse."""
+    lse = torch.empty((B * num_heads * Lq,), dtype=torch.float32, device=device)
+    rc = _lib.load().fmmt_mha_fwd(code, Lq, Lk, B, E, num_heads, qp, ldq, kp, vp, ldkv, scale, _p(key_bias), dropout_p, seed_i, seedp, outp, ldo,
+                                  _p(lse), _st())
+    check(rc, f"fmmt_mha_fwd({what}Lq={Lq},Lk={Lk},B={B},E={E},heads={num_heads})")
+    return lse
+
+
+def mha_bwd_ptrs(code, Lq, Lk, B, E, num_heads, qp, ldq, kp, vp, ldkv, scale, key_bias, dropout_p, seed_i, seedp, outp, doutp, ldo, lse, dqp, dkp, dvp,
+                 what=""):
+    """THE call of fmmt_mha_bwd, as mha_fwd_ptrs; the gradients at dqp / dkp / dvp are laid out as their operands (pitches ldq / ldkv)"""
+    rc = _lib.load().fmmt_mha_bwd(code, Lq, Lk, B, E, num_heads, qp, ldq, kp, vp, ldkv, scale, _p(key_bias), dropout_p, seed_i, seedp, outp, doutp, ldo,
+                                  _p(lse), dqp, ldq, dkp, dvp, ldkv, _st())
+    check(rc, f"fmmt_mha_bwd({what}Lq={Lq},Lk={Lk},B={B},E={E},heads={num_heads})")
+
+
+def _cols(t, E, n):
+    """the addresses of the first n E-wide column slices of a packed tensor (rows [a | b | ...])"""
+    return tuple(t.data_ptr() + i * E * t.element_size() for i in range(n))
+
+
+def _kv_ptrs(k, v, E):
+    """(k address, v address, row pitch) of separate (Lk, B, E) k, v -- or of the packed (Lk, B, 2E) [k | v] projection k when v is None"""
+    return (*_cols(k, E, 2), 2 * E) if v is None else (k.data_ptr(), v.data_ptr(), E)
+
+
+def _packed_qkv(qkv, E):
+    """(q address, its pitch, k address, v address, their pitch) of a packed projection, rows [q | k | v]"""
+    qp, kp, vp = _cols(qkv, E, 3)
+    return qp, 3 * E, kp, vp, 3 * E
 
 
 def mha_fwd_raw(q, k, v, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
     """fmmt_mha_fwd on contiguous time-major operands; v None = k is the packed [k | v] projection.  Returns (out, lse)."""
     Lq, B, E = q.shape
-    packed, Lk, ldkv, kp, vp = _mha_ptrs(k, v, E)
     out = torch.empty_like(q)
-    lse = torch.empty((B * num_heads * Lq,), dtype=torch.float32, device=q.device)
-    rc = _lib.load().fmmt_mha_fwd(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, _p(q), E, kp, vp, ldkv, scale, _p(key_bias),
-                                  dropout_p, seed_i, _p(seed_t), _p(out), E, _p(lse), _st())
-    check(rc, f"fmmt_mha_fwd(Lq={Lq},Lk={Lk},B={B},E={E},heads={num_heads})")
+    lse = mha_fwd_ptrs(dtype_code(q.dtype), Lq, k.shape[0], B, E, num_heads, _p(q), E, *_kv_ptrs(k, v, E), scale, key_bias, dropout_p, seed_i, _p(seed_t),
+                       _p(out), E, q.device)
     return out, lse
 
 
 def mha_bwd_raw(q, k, v, out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
     """fmmt_mha_bwd; returns (dq, dk, dv) with dv None when k is the packed projection (dk then holds [dk | dv])"""
     Lq, B, E = q.shape
-    packed, Lk, ldkv, kp, vp = _mha_ptrs(k, v, E)
-    dq = torch.empty_like(q)
-    dk = torch.empty_like(k)
-    if packed:
-        dkp, dvp, dv = dk.data_ptr(), dk.data_ptr() + E * k.element_size(), None
-    else:
-        dv = torch.empty_like(v)
-        dkp, dvp = dk.data_ptr(), dv.data_ptr()
-    rc = _lib.load().fmmt_mha_bwd(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, _p(q), E, kp, vp, ldkv, scale, _p(key_bias),
-                                  dropout_p, seed_i, _p(seed_t), _p(out), _p(dout), E, _p(lse), _p(dq), E, dkp, dvp, ldkv, _st())
-    check(rc, "fmmt_mha_bwd")
+    dq, dk = torch.empty_like(q), torch.empty_like(k)
+    dv = torch.empty_like(v) if v is not None else None
+    mha_bwd_ptrs(dtype_code(q.dtype), Lq, k.shape[0], B, E, num_heads, _p(q), E, *_kv_ptrs(k, v, E), scale, key_bias, dropout_p, seed_i, _p(seed_t),
+                 _p(out), _p(dout), E, lse, _p(dq), *_kv_ptrs(dk, dv, E)[:2])
     return dq, dk, dv
 
 
-def mha_packed_bm_fwd_raw(qkv, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
-    """fmmt_mha_fwd(dtype | FMMT_BATCH_MAJOR) of SELF-attention over a packed batch-major projection qkv (B, S, 3E) = [q | k | v]: the three operands are
-    column slices of it (row pitch 3E), nothing is transposed or copied.  Returns (out (B, S, E), lse)."""
-    B, S, E3 = qkv.shape
-    E = E3 // 3
-    es = qkv.element_size()
-    out = torch.empty((B, S, E), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((B * num_heads * S,), dtype=torch.float32, device=qkv.device)
-    qp = qkv.data_ptr()
-    rc = _lib.load().fmmt_mha_fwd(dtype_code(qkv.dtype) | _lib.BATCH_MAJOR, S, S, B, E, num_heads, qp, E3, qp + E * es, qp + 2 * E * es, E3, scale, _p(key_bias),
-                                  dropout_p, seed_i, _p(seed_t), _p(out), E, _p(lse), _st())
-    check(rc, f"fmmt_mha_fwd(batch-major, S={S},B={B},E={E},heads={num_heads})")
+def mha_packed_fwd_raw(qkv, L, B, num_heads, scale, dropout_p, seed_i, seed_t, key_bias, batch_major=False):
+    """fmmt_mha_fwd of SELF-attention over a packed projection, rows [q | k | v] of 3E columns: the three operands are column slices of it (row
+    pitch 3E), nothing is transposed or copied.  Rows in (l, b) order, or with batch_major (dtype | FMMT_BATCH_MAJOR) in (b, l) order.
+    Returns (out -- (B, L, E) batch-major, (L, B, E) otherwise --, lse)."""
+    E = qkv.shape[-1] // 3
+    out = torch.empty((B, L, E) if batch_major else (L, B, E), dtype=qkv.dtype, device=qkv.device)
+    lse = mha_fwd_ptrs(dtype_code(qkv.dtype) | (_lib.BATCH_MAJOR if batch_major else 0), L, L, B, E, num_heads, *_packed_qkv(qkv, E), scale, key_bias,
+                       dropout_p, seed_i, _p(seed_t), _p(out), E, qkv.device, "batch-major, " if batch_major else "self, ")
     return out, lse
 
 
-def mha_packed_bm_bwd_raw(qkv, out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
-    """fmmt_mha_bwd(dtype | FMMT_BATCH_MAJOR): the gradient of the packed projection, (B, S, 3E) = [dq | dk | dv], written in place by the two kernels"""
-    B, S, E3 = qkv.shape
-    E = E3 // 3
-    es = qkv.element_size()
+def mha_packed_bwd_raw(qkv, L, B, out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias, batch_major=False):
+    """fmmt_mha_bwd of mha_packed_fwd_raw: the gradient of the packed projection, rows [dq | dk | dv], written in place by the two kernels"""
+    E = qkv.shape[-1] // 3
     dqkv = torch.empty_like(qkv)
-    qp, dp = qkv.data_ptr(), dqkv.data_ptr()
-    rc = _lib.load().fmmt_mha_bwd(dtype_code(qkv.dtype) | _lib.BATCH_MAJOR, S, S, B, E, num_heads, qp, E3, qp + E * es, qp + 2 * E * es, E3, scale, _p(key_bias),
-                                  dropout_p, seed_i, _p(seed_t), _p(out), _p(dout), E, _p(lse), dp, E3, dp + E * es, dp + 2 * E * es, E3, _st())
-    check(rc, f"fmmt_mha_bwd(batch-major, S={S},B={B},E={E},heads={num_heads})")
+    mha_bwd_ptrs(dtype_code(qkv.dtype) | (_lib.BATCH_MAJOR if batch_major else 0), L, L, B, E, num_heads, *_packed_qkv(qkv, E), scale, key_bias,
+                 dropout_p, seed_i, _p(seed_t), _p(out), _p(dout), E, lse, *_cols(dqkv, E, 3), "batch-major, " if batch_major else "self, ")
     return dqkv
+
+
+def mha_packed_bm_fwd_raw(qkv, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
+    """mha_packed_fwd_raw over a batch-major qkv (B, S, 3E).  Returns (out (B, S, E), lse)."""
+    return mha_packed_fwd_raw(qkv, qkv.shape[1], qkv.shape[0], num_heads, scale, dropout_p, seed_i, seed_t, key_bias, batch_major=True)
+
+
+def mha_packed_bm_bwd_raw(qkv, out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
+    """mha_packed_bwd_raw over a batch-major qkv (B, S, 3E): (B, S, 3E) = [dq | dk | dv]"""
+    return mha_packed_bwd_raw(qkv, qkv.shape[1], qkv.shape[0], out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias, batch_major=True)
 
 
 class MhaCoreFn(Function):
@@ -1281,8 +1270,7 @@ class MhaCoreFn(Function):
         Lq, B, E = q.shape
         k = k.contiguous()
         v = v.contiguous() if v is not None else None
-        seed_t = seed if isinstance(seed, torch.Tensor) else None          # device int64 word: graph-replay safe
-        seed_i = 0 if seed_t is not None else int(seed)
+        seed_i, seed_t = _seed_args(seed)
         if key_bias is not None:
             key_bias = key_bias.detach().to(torch.float32).contiguous()
             assert key_bias.shape == (B, k.shape[0]), f"key_bias must be (B, Lk) = ({B}, {k.shape[0]}), got {tuple(key_bias.shape)}"
@@ -1298,6 +1286,11 @@ class MhaCoreFn(Function):
         num_heads, scale, dropout_p, seed = ctx.cfg
         dq, dk, dv = mha_bwd_raw(q, k, v, out, dout.contiguous(), lse, num_heads, scale, dropout_p, seed, seed_t, key_bias)
         return dq, dk, dv, None, None, None, None, None
+
+
+def _seg_seed(seed, seed_t, i):
+    """(seed_i, address of the seed word) of segment i: word i of the device seeds, or the integer seed + i"""
+    return (0, seed_t.data_ptr() + 8 * i) if seed_t is not None else (int(seed) + i, None)
 
 
 class MhaSegFn(Function):
@@ -1324,15 +1317,10 @@ class MhaSegFn(Function):
         es = q.element_size()
         out = torch.empty_like(q)
         lses = []
-        lib = _lib.load()
         for i, (q0, Lq, k0, Lk) in enumerate(segs):
-            lse = torch.empty((B * num_heads * Lq,), dtype=torch.float32, device=q.device)
-            kp = kv.data_ptr() + k0 * B * 2 * E * es
-            rc = lib.fmmt_mha_fwd(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, q.data_ptr() + q0 * B * E * es, E, kp, kp + E * es, 2 * E, scale, None,
-                                  dropout_p, 0 if seed_t is not None else int(seed) + i, (seed_t.data_ptr() + 8 * i) if seed_t is not None else None,
-                                  out.data_ptr() + q0 * B * E * es, E, _p(lse), _st())
-            check(rc, f"fmmt_mha_fwd(segment {i}: Lq={Lq},Lk={Lk},B={B},E={E},heads={num_heads})")
-            lses.append(lse)
+            qo, kp = q0 * B * E * es, kv.data_ptr() + k0 * B * 2 * E * es
+            lses.append(mha_fwd_ptrs(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, q.data_ptr() + qo, E, kp, kp + E * es, 2 * E, scale, None, dropout_p,
+                                     *_seg_seed(seed, seed_t, i), out.data_ptr() + qo, E, q.device, f"segment {i}: "))
         ctx.save_for_backward(q, kv, out, seed_t, *lses)
         ctx.cfg = (tuple(segs), num_heads, scale, dropout_p, 0 if seed_t is not None else int(seed))
         return out
@@ -1345,20 +1333,31 @@ class MhaSegFn(Function):
         es = q.element_size()
         dout = dout.contiguous()
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        lib = _lib.load()
         for i, (q0, Lq, k0, Lk) in enumerate(segs):
             qo, ko = q0 * B * E * es, k0 * B * 2 * E * es
-            rc = lib.fmmt_mha_bwd(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, q.data_ptr() + qo, E, kv.data_ptr() + ko, kv.data_ptr() + ko + E * es, 2 * E,
-                                  scale, None, dropout_p, seed + i if seed_t is None else 0, (seed_t.data_ptr() + 8 * i) if seed_t is not None else None,
-                                  out.data_ptr() + qo, dout.data_ptr() + qo, E, _p(lses[i]), dq.data_ptr() + qo, E, dkv.data_ptr() + ko,
-                                  dkv.data_ptr() + ko + E * es, 2 * E, _st())
-            check(rc, f"fmmt_mha_bwd(segment {i})")
+            kp, dkp = kv.data_ptr() + ko, dkv.data_ptr() + ko
+            mha_bwd_ptrs(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, q.data_ptr() + qo, E, kp, kp + E * es, 2 * E, scale, None, dropout_p,
+                         *_seg_seed(seed, seed_t, i), out.data_ptr() + qo, dout.data_ptr() + qo, E, lses[i], dq.data_ptr() + qo, dkp, dkp + E * es,
+                         f"segment {i}: ")
         return dq, dkv, None, None, None, None, None
 
 
 def mha_core_segments(q, kv, segs, num_heads, scale, dropout_p=0.0, seed=0):
     return MhaSegFn.apply(q, kv, tuple(tuple(int(v) for v in s) for s in segs), num_heads, scale, float(dropout_p),
                           seed if isinstance(seed, torch.Tensor) else int(seed))
+
+
+def linear_seg3_raw(x2, ws, bs, y, seg_mode):
+    """fmmt_linear_fwd_seg3 into y (M, N) from x2 (M, K) and three weights of one dtype.  seg_mode 1: y[:, s N/3:(s+1) N/3] = x2 ws[s]^T + bs[s],
+    ws[s] (N/3, K), bs[s] fp32 or None; seg_mode 2: y = sum_s x2[:, s K/3:(s+1) K/3] ws[s]^T, ws[s] (N, K/3), no bias.  False (nothing launched)
+    where the library does not take the shape -- FMMT_EINVAL: the caller issues three linear_raw calls instead."""
+    (M, K), N = x2.shape, y.shape[1]
+    rc = _lib.load().fmmt_linear_fwd_seg3(dtype_code(x2.dtype), M, N, K, _p(x2), K, _p(ws[0]), _p(ws[1]), _p(ws[2]), ws[0].shape[1], seg_mode,
+                                          _p(bs[0]), _p(bs[1]), _p(bs[2]), _p(y), N, _st())
+    if rc == _lib.FMMT_EINVAL:
+        return False
+    check(rc, f"fmmt_linear_fwd_seg3(M={M},N={N},K={K})")
+    return True
 
 
 class SelfAttnQkvFn(Function):
@@ -1377,29 +1376,17 @@ class SelfAttnQkvFn(Function):
         L, B, H = x.shape
         M = L * B
         x2 = x.reshape(M, H)
-        lib = _lib.load()
         ws = [_lp(w, x.dtype) for w in (wq, wk, wv)]
         bs = [b.detach().float().contiguous() if b is not None else None for b in (bq, bk, bv)]
         qkv = torch.empty((M, 3 * H), dtype=x.dtype, device=x.device)
-        rc = lib.fmmt_linear_fwd_seg3(dtype_code(x.dtype), M, 3 * H, H, _p(x2), H, _p(ws[0]), _p(ws[1]), _p(ws[2]), H, 1, _p(bs[0]), _p(bs[1]), _p(bs[2]),
-                                      _p(qkv), 3 * H, _st())
-        if rc == _lib.FMMT_EINVAL:
+        if not linear_seg3_raw(x2, ws, bs, qkv, 1):
             for i in range(3):
                 qkv[:, i * H:(i + 1) * H] = linear_raw(x2, ws[i], bs[i])
-        else:
-            check(rc, f"fmmt_linear_fwd_seg3(M={M},N={3 * H},K={H})")
-        seed_t = seed if isinstance(seed, torch.Tensor) else None
-        seed_i = 0 if seed_t is not None else int(seed)
+        seed_i, seed_t = _seed_args(seed)
         if key_bias is not None:
             key_bias = key_bias.detach().to(torch.float32).contiguous()
             assert key_bias.shape == (B, L)
-        es = x.element_size()
-        out = torch.empty_like(x)
-        lse = torch.empty((B * num_heads * L,), dtype=torch.float32, device=x.device)
-        qp = qkv.data_ptr()
-        rc = lib.fmmt_mha_fwd(dtype_code(x.dtype), L, L, B, H, num_heads, qp, 3 * H, qp + H * es, qp + 2 * H * es, 3 * H, scale, _p(key_bias),
-                              dropout_p, seed_i, _p(seed_t), _p(out), H, _p(lse), _st())
-        check(rc, f"fmmt_mha_fwd(self, L={L},B={B},H={H},heads={num_heads})")
+        out, lse = mha_packed_fwd_raw(qkv, L, B, num_heads, scale, dropout_p, seed_i, seed_t, key_bias)
         ctx.save_for_backward(x2, qkv, out, lse, seed_t, key_bias, wq, wk, wv)
         ctx.cfg = (num_heads, scale, dropout_p, seed_i, (L, B, H), tuple(b is not None for b in bs))
         return out
@@ -1408,24 +1395,13 @@ class SelfAttnQkvFn(Function):
     def backward(ctx, dout):
         x2, qkv, out, lse, seed_t, key_bias, wq, wk, wv = ctx.saved_tensors
         num_heads, scale, dropout_p, seed_i, (L, B, H), has_b = ctx.cfg
-        M = L * B
-        lib = _lib.load()
-        es = x2.element_size()
-        dout = dout.contiguous()
-        dqkv = torch.empty_like(qkv)
-        qp, dp = qkv.data_ptr(), dqkv.data_ptr()
-        rc = lib.fmmt_mha_bwd(dtype_code(x2.dtype), L, L, B, H, num_heads, qp, 3 * H, qp + H * es, qp + 2 * H * es, 3 * H, scale, _p(key_bias),
-                              dropout_p, seed_i, _p(seed_t), _p(out), _p(dout), H, _p(lse), dp, 3 * H, dp + H * es, dp + 2 * H * es, 3 * H, _st())
-        check(rc, "fmmt_mha_bwd(self)")
+        dqkv = mha_packed_bwd_raw(qkv, L, B, out, dout.contiguous(), lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias)
         dx = None
         if ctx.needs_input_grad[0]:
             wt = [_lp(w, x2.dtype, transpose=True) for w in (wq, wk, wv)]
             dx = torch.empty_like(x2)
-            rc = lib.fmmt_linear_fwd_seg3(dtype_code(x2.dtype), M, H, 3 * H, dp, 3 * H, _p(wt[0]), _p(wt[1]), _p(wt[2]), H, 2, None, None, None, _p(dx), H, _st())
-            if rc == _lib.FMMT_EINVAL:
+            if not linear_seg3_raw(dqkv, wt, (None, None, None), dx, 2):
                 dx = sum(linear_raw(dqkv[:, i * H:(i + 1) * H].contiguous(), wt[i], None) for i in range(3))
-            else:
-                check(rc, f"fmmt_linear_fwd_seg3(M={M},N={H},K={3 * H})")
             dx = dx.reshape(L, B, H)
         dw, db = wgrad_raw(dqkv, x2, True)
         g = []
@@ -1544,8 +1520,7 @@ def mha_avg_weights(q, k, lse, num_heads, scale, dropout_p=0.0, seed=0, key_bias
     k = k.detach().contiguous()
     Lq, B, E = q.shape
     Lk, ldkv = k.shape[0], k.shape[2]
-    seed_t = seed if isinstance(seed, torch.Tensor) else None
-    seed_i = 0 if seed_t is not None else int(seed)
+    seed_i, seed_t = _seed_args(seed)
     kb = key_bias.detach().to(torch.float32).contiguous() if key_bias is not None else None
     w = torch.empty((B, Lq, Lk), dtype=torch.float32, device=q.device)
     rc = _lib.load().fmmt_mha_avg_weights(dtype_code(q.dtype), Lq, Lk, B, E, num_heads, _p(q), E, _p(k), ldkv, scale, _p(kb), float(dropout_p),
@@ -1731,16 +1706,7 @@ class PatchEmbedU8LnFn(Function):
     @staticmethod
     def backward(ctx, dy):
         cols, weight, x_pre, mean, rstd, g = ctx.saved_tensors
-        M, C = x_pre.shape
-        lib = _lib.load()
-        dy = dy.contiguous()
-        dxp = torch.empty_like(x_pre)
-        dg = torch.empty(C, dtype=torch.float32, device=dy.device)
-        db = torch.empty(C, dtype=torch.float32, device=dy.device)
-        nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-        ws = _ws(nbytes, dy.device)
-        check(lib.fmmt_layernorm_bwd(dtype_code(dy.dtype), M, C, _p(dy), _p(x_pre), _p(mean), _p(rstd), _p(g), None, _p(dxp), _p(dg), _p(db), 0,
-                                     _p(ws), nbytes, _st()), f"fmmt_layernorm_bwd(patch embed, M={M})")
+        dxp, dg, db = layernorm_bwd_raw(dy.contiguous(), x_pre, mean, rstd, g)
         dw, dbias = wgrad_raw(dxp, cols, ctx.has_bias)
         return None, None, dw.view_as(weight), dbias, dg, db, None, None, None, None, None
 
@@ -1871,26 +1837,32 @@ class BatchNorm1dNFn(Function):
         return dx, dg, db, None, None, None, None, None, None
 
 
+def posemb_scale_fwd_raw(x, table, scale):
+    """fmmt_posemb_scale_fwd on a contiguous time-major x (L, B, E): y = scale * x + table[position], position of (t, b) = t + 1 where
+    x[t, b, 0] != 0, else 0 (CrossmodalTransformer.py:63-66)"""
+    L, B, E = x.shape
+    y = torch.empty_like(x)
+    check(_lib.load().fmmt_posemb_scale_fwd(dtype_code(x.dtype), L, B, E, _p(x), _p(table), scale, _p(y), _st()), f"fmmt_posemb_scale_fwd(L={L},B={B},E={E})")
+    return y
+
+
+def scale_raw(x, scale):
+    """fmmt_scale: scale * x of a contiguous x"""
+    y = torch.empty_like(x)
+    check(_lib.load().fmmt_scale(dtype_code(x.dtype), x.numel(), _p(x), scale, _p(y), _st()), f"fmmt_scale(n={x.numel()})")
+    return y
+
+
 class PosEmbScaleFn(Function):
     @staticmethod
     def forward(ctx, x, table, scale):
         _need_cuda(x, "positional_embedding")
-        lib = _lib.load()
-        x = x.contiguous()
-        L, B, E = x.shape
-        y = torch.empty_like(x)
-        check(lib.fmmt_posemb_scale_fwd(dtype_code(x.dtype), L, B, E, _p(x), _p(table), scale, _p(y), _st()),
-              f"fmmt_posemb_scale_fwd(L={L},B={B},E={E})")
         ctx.scale = scale
-        return y
+        return posemb_scale_fwd_raw(x.contiguous(), table, scale)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        dy = dy.contiguous()
-        dx = torch.empty_like(dy)
-        check(lib.fmmt_scale(dtype_code(dy.dtype), dy.numel(), _p(dy), ctx.scale, _p(dx), _st()), "fmmt_scale")
-        return dx, None, None
+        return scale_raw(dy.contiguous(), ctx.scale), None, None
 
 
 def posemb_scale(x, table, scale):
@@ -2088,8 +2060,7 @@ def pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p
     pooled, keep = torch.empty((B, H), dtype=torch.float32, device=dev), torch.empty((B, H), dtype=torch.float32, device=dev)
     nbytes = lib.fmmt_pool_head_bwd_workspace(B, L, H)
     ws = _ws(nbytes, dev)
-    seed_t = seed if isinstance(seed, torch.Tensor) else None
-    seed_i = 0 if seed_t is not None else int(seed)
+    seed_i, seed_t = _seed_args(seed)
     if valid_mean:
         n_rows = torch.empty((1,), dtype=torch.int32, device=dev)
         check(lib.fmmt_pool_head_fwd_rows(dtype_code(h2.dtype), B, L, H, NL, _p(h2), _p(ph2), _p(q), _p(vw), _p(vb), _p(mk), _p(cw), _p(cb), _p(lab), float(p),

@@ -48,6 +48,14 @@ def _cast(w: Tensor, dtype, transpose: bool = False) -> Tensor:
     return w.t().contiguous() if transpose else w.contiguous()
 
 
+def _shift_mask(H: int, W: int, shift: int, device) -> Optional[Tensor]:
+    """the standard SW-MSA mask of (H, W, shift) on `device` (fp32, (nW, 49, 49)); None without a shift"""
+    if not shift:
+        return None
+    from .modules.SwinTransformer.Swin_Transformer import build_shift_mask
+    return build_shift_mask(H, W, 7, shift).to(device)
+
+
 # ------------------------------------------------------------------------------------------------ linear
 @torch.library.custom_op(f"{_LIB}::linear", mutates_args=(), device_types="cuda")
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], res: Optional[Tensor], rowscale: Optional[Tensor], rows_per_scale: int) -> Tensor:
@@ -134,19 +142,7 @@ mlp.register_autograd(_mlp_backward, setup_context=_mlp_setup)
 # ------------------------------------------------------------------------------------------------ layer_norm
 @torch.library.custom_op(f"{_LIB}::layer_norm", mutates_args=(), device_types="cuda")
 def layer_norm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float) -> Tuple[Tensor, Tensor, Tensor]:
-    from . import _lib
-    lib = _lib.load()
-    x = x.contiguous()
-    C = x.shape[-1]
-    M = x.numel() // C
-    y = torch.empty_like(x)
-    mean = torch.empty(M, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    g, b = gamma.float().contiguous(), beta.float().contiguous()
-    rc = lib.fmmt_layernorm_fwd(_lib.dtype_code(x.dtype), M, C, x.data_ptr(), g.data_ptr(), b.data_ptr(), eps, y.data_ptr(), mean.data_ptr(),
-                                rstd.data_ptr(), 0, ops._st())
-    _lib.check(rc, f"fmmt_layernorm_fwd(M={M},C={C})")
-    return y, mean, rstd
+    return ops.layernorm_fwd_raw(x.contiguous(), gamma.float().contiguous(), beta.float().contiguous(), eps)
 
 
 @layer_norm.register_fake
@@ -163,22 +159,8 @@ def _ln_setup(ctx, inputs, output):
 
 
 def _ln_backward(ctx, dy, _dmean, _drstd):
-    from . import _lib
     x, mean, rstd, gamma = ctx.saved_tensors
-    lib = _lib.load()
-    x = x.contiguous()
-    C = x.shape[-1]
-    M = x.numel() // C
-    dy = dy.contiguous()
-    g = gamma.float().contiguous()
-    dx = torch.empty_like(x)
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty(C, dtype=torch.float32, device=x.device)
-    nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-    ws = ops._ws(nbytes, x.device)
-    rc = lib.fmmt_layernorm_bwd(_lib.dtype_code(x.dtype), M, C, dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g.data_ptr(), None,
-                                dx.data_ptr(), dg.data_ptr(), db.data_ptr(), 0, ws.data_ptr(), nbytes, ops._st())
-    _lib.check(rc, f"fmmt_layernorm_bwd(M={M},C={C})")
+    dx, dg, db = ops.layernorm_bwd_raw(dy.contiguous(), x.contiguous(), mean, rstd, gamma.float().contiguous())
     return dx, dg, db, None
 
 
@@ -191,23 +173,8 @@ def window_attention(qkv: Tensor, table: Tensor, index_i32: Tensor, n_img: int, 
                      scale: float) -> Tuple[Tensor, Tensor]:
     """qkv (n_img*H*W, 3C) in token order; table (169, heads) fp32; the shift mask is the standard SW-MSA one (derived from
     the window coordinates inside the kernel)."""
-    from . import _lib
-    lib = _lib.load()
-    qkv = qkv.contiguous()
-    C = qkv.shape[-1] // 3
-    nW = (H // 7) * (W // 7)
-    out = torch.empty((n_img * H * W, C), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((n_img * nW * num_heads * 49,), dtype=torch.float32, device=qkv.device)
-    tab = table.float().contiguous()
-    mask = None
-    if shift:
-        from .modules.SwinTransformer.Swin_Transformer import build_shift_mask
-        mask = build_shift_mask(H, W, 7, shift).to(qkv.device)
-    rc = lib.fmmt_window_attn_fwd(_lib.dtype_code(qkv.dtype), n_img, H, W, C, num_heads, shift, qkv.data_ptr(), tab.data_ptr(), index_i32.data_ptr(),
-                                  mask.data_ptr() if mask is not None else None, nW if mask is not None else 0, 1 if mask is not None else 0,
-                                  scale, out.data_ptr(), lse.data_ptr(), ops._st())
-    _lib.check(rc, "fmmt_window_attn_fwd")
-    return out, lse
+    return ops.window_attn_fwd_raw(qkv.contiguous(), table.float().contiguous(), index_i32, _shift_mask(H, W, shift, qkv.device), n_img, H, W, num_heads,
+                                   shift, scale, bool(shift))
 
 
 @window_attention.register_fake
@@ -225,28 +192,10 @@ def _wa_setup(ctx, inputs, output):
 
 
 def _wa_backward(ctx, dout, _dlse):
-    from . import _lib
     qkv, out, lse, table, index_i32 = ctx.saved_tensors
     n_img, H, W, num_heads, shift, scale = ctx.cfg
-    lib = _lib.load()
-    qkv = qkv.contiguous()
-    C = qkv.shape[-1] // 3
-    nW = (H // 7) * (W // 7)
-    tab = table.float().contiguous()
-    mask = None
-    if shift:
-        from .modules.SwinTransformer.Swin_Transformer import build_shift_mask
-        mask = build_shift_mask(H, W, 7, shift).to(qkv.device)
-    dout = dout.contiguous()
-    dqkv = torch.empty_like(qkv)
-    dtable = torch.empty_like(tab)
-    nbytes = lib.fmmt_window_attn_bwd_workspace(num_heads)
-    ws = ops._ws(nbytes, qkv.device)
-    rc = lib.fmmt_window_attn_bwd(_lib.dtype_code(qkv.dtype), n_img, H, W, C, num_heads, shift, qkv.data_ptr(), out.data_ptr(), dout.data_ptr(),
-                                  lse.data_ptr(), tab.data_ptr(), index_i32.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                  nW if mask is not None else 0, 1 if mask is not None else 0, scale, dqkv.data_ptr(), dtable.data_ptr(),
-                                  ws.data_ptr(), nbytes, ops._st())
-    _lib.check(rc, "fmmt_window_attn_bwd")
+    dqkv, dtable = ops.window_attn_bwd_raw(qkv.contiguous(), out, dout.contiguous(), lse, table.float().contiguous(), index_i32,
+                                           _shift_mask(H, W, shift, qkv.device), n_img, H, W, num_heads, shift, scale, bool(shift))
     return dqkv, dtable.to(table.dtype), None, None, None, None, None, None, None
 
 
@@ -285,31 +234,10 @@ def _(img_u8, flavour, bf16, augment):
 
 
 # ------------------------------------------------------------------------------------------------ PatchMerging gather + LayerNorm
-def _ln_call(x, gamma, beta, eps, merge_hw):
-    from . import _lib
-    lib = _lib.load()
-    x = x.contiguous()
-    if merge_hw:
-        n, L, Cq = x.shape
-        M, C = n * (merge_hw // 2) ** 2, 4 * Cq
-        y = torch.empty((n, (merge_hw // 2) ** 2, C), dtype=x.dtype, device=x.device)
-    else:
-        C = x.shape[-1]
-        M = x.numel() // C
-        y = torch.empty_like(x)
-    mean = torch.empty(M, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-    g, b = gamma.float().contiguous(), beta.float().contiguous()
-    rc = lib.fmmt_layernorm_fwd(_lib.dtype_code(x.dtype), M, C, x.data_ptr(), g.data_ptr(), b.data_ptr(), eps, y.data_ptr(), mean.data_ptr(),
-                                rstd.data_ptr(), merge_hw, ops._st())
-    _lib.check(rc, f"fmmt_layernorm_fwd(M={M},C={C},merge={merge_hw})")
-    return y, mean, rstd
-
-
 @torch.library.custom_op(f"{_LIB}::layer_norm_merge", mutates_args=(), device_types="cuda")
 def layer_norm_merge(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, merge_hw: int) -> Tuple[Tensor, Tensor, Tensor]:
     """x (n, H*W, C/4) token grid, H = W = merge_hw -> LayerNorm over the 2x2-neighbour concat (n, H*W/4, C)  (Swin_Transformer.py:316-325)"""
-    return _ln_call(x, gamma, beta, eps, merge_hw)
+    return ops.layernorm_fwd_raw(x.contiguous(), gamma.float().contiguous(), beta.float().contiguous(), eps, merge_hw)
 
 
 @layer_norm_merge.register_fake
@@ -328,22 +256,8 @@ def _lnm_setup(ctx, inputs, output):
 
 
 def _lnm_backward(ctx, dy, _dmean, _drstd):
-    from . import _lib
     x, mean, rstd, gamma = ctx.saved_tensors
-    lib = _lib.load()
-    x = x.contiguous()
-    n, L, Cq = x.shape
-    M, C = n * (ctx.merge_hw // 2) ** 2, 4 * Cq
-    dy = dy.contiguous()
-    g = gamma.float().contiguous()
-    dx = torch.empty_like(x)
-    dg = torch.empty(C, dtype=torch.float32, device=x.device)
-    db = torch.empty(C, dtype=torch.float32, device=x.device)
-    nbytes = lib.fmmt_layernorm_bwd_workspace(C)
-    ws = ops._ws(nbytes, x.device)
-    rc = lib.fmmt_layernorm_bwd(_lib.dtype_code(x.dtype), M, C, dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g.data_ptr(), None,
-                                dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ctx.merge_hw, ws.data_ptr(), nbytes, ops._st())
-    _lib.check(rc, f"fmmt_layernorm_bwd(M={M},C={C},merge={ctx.merge_hw})")
+    dx, dg, db = ops.layernorm_bwd_raw(dy.contiguous(), x.contiguous(), mean, rstd, gamma.float().contiguous(), merge_hw=ctx.merge_hw)
     return dx, dg, db, None, None
 
 
@@ -457,13 +371,7 @@ mha.register_autograd(_mha_backward, setup_context=_mha_setup)
 @torch.library.custom_op(f"{_LIB}::posemb_scale", mutates_args=(), device_types="cuda")
 def posemb_scale(x: Tensor, table: Tensor, scale: float) -> Tensor:
     """y = scale * x + table[position], position of (t, b) = t + 1 where x[t, b, 0] != 0, else 0 (CrossmodalTransformer.py:63-66)"""
-    from . import _lib
-    x = x.contiguous()
-    L, B, E = x.shape
-    y = torch.empty_like(x)
-    _lib.check(_lib.load().fmmt_posemb_scale_fwd(_lib.dtype_code(x.dtype), L, B, E, x.data_ptr(), table.data_ptr(), scale, y.data_ptr(), ops._st()),
-               f"fmmt_posemb_scale_fwd(L={L},B={B},E={E})")
-    return y
+    return ops.posemb_scale_fwd_raw(x.contiguous(), table, scale)
 
 
 @posemb_scale.register_fake
@@ -476,11 +384,7 @@ def _pe_setup(ctx, inputs, output):
 
 
 def _pe_backward(ctx, dy):
-    from . import _lib
-    dy = dy.contiguous()
-    dx = torch.empty_like(dy)
-    _lib.check(_lib.load().fmmt_scale(_lib.dtype_code(dy.dtype), dy.numel(), dy.data_ptr(), ctx.scale, dx.data_ptr(), ops._st()), "fmmt_scale")
-    return dx, None, None
+    return ops.scale_raw(dy.contiguous(), ctx.scale), None, None
 
 
 posemb_scale.register_autograd(_pe_backward, setup_context=_pe_setup)
@@ -494,10 +398,7 @@ def window_block(x: Tensor, ln_w: Tensor, ln_b: Tensor, eps: float, wqkv: Tensor
     """y = x + rowscale * (proj(W-MSA(LN(x) wqkv^T + bqkv)) + bproj) (bf16; C = 96: one launch, fmmt_window_block_fwd; C = 192: four launches); shift > 0 uses the
     standard SW-MSA mask of (H, W, shift).  Also returns LN(x), the attention output, the row statistics and the log-sum-exp."""
     C = x.shape[-1]
-    mask = None
-    if shift:
-        from .modules.SwinTransformer.Swin_Transformer import build_shift_mask
-        mask = build_shift_mask(H, W, 7, shift).to(x.device)
+    mask = _shift_mask(H, W, shift, x.device)
     y, xn, o, mean, rstd, lse = ops.window_block_raw(
         x.reshape(-1, C).contiguous(), n_img, H, W, num_heads, shift, ln_w.float().contiguous(), ln_b.float().contiguous(), eps, _cast(wqkv, x.dtype),
         bqkv.float().contiguous() if bqkv is not None else None, _cast(wproj, x.dtype), bproj.float().contiguous() if bproj is not None else None,
@@ -525,10 +426,7 @@ def _wb_setup(ctx, inputs, output):
 def _wb_backward(ctx, dy, *_unused):
     x, xn, o, mean, rstd, lse, ln_w, wqkv, bqkv, wproj, table, index_i32, rowscale = ctx.saved_tensors
     n_img, H, W, num_heads, shift, scale, has_bproj = ctx.cfg
-    mask = None
-    if shift:
-        from .modules.SwinTransformer.Swin_Transformer import build_shift_mask
-        mask = build_shift_mask(H, W, 7, shift).to(x.device)
+    mask = _shift_mask(H, W, shift, x.device)
     C = x.shape[-1]
     g = ops.window_block_backward(dy, x.reshape(-1, C).contiguous(), xn, o, mean, rstd, lse, ln_w.float().contiguous(), wqkv, bqkv, wproj,
                                   table.float().contiguous(), index_i32, mask, rowscale, (n_img, H, W, C, num_heads, shift, scale, x.shape))

@@ -969,7 +969,7 @@ class FusedHandOver:
     @torch.no_grad()
     def __call__(self, pairs, flat_view_of, accumulate: bool, norm_out) -> bool:
         import numpy as np
-        from . import _lib
+        from . import ops
         grads = []
         for p, master in pairs:
             g = p.grad
@@ -1000,9 +1000,7 @@ class FusedHandOver:
         table = torch.empty(raw.numel(), dtype=torch.uint8, device=dev)
         table.copy_(host, non_blocking=True)
         partial = torch.empty(blocks, dtype=torch.float32, device=dev)
-        rc = _lib.load().fmmt_grad_handover(len(grads), blocks, table.data_ptr(), partial.data_ptr(), norm_out.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(rc, "fmmt_grad_handover")
+        ops.grad_handover_raw(len(grads), blocks, table, partial, norm_out)
         self.keep = self.keep[-3:] + [(table, partial)]
         for p, _ in pairs:
             p.grad = None
@@ -1169,9 +1167,7 @@ class FusedClipAdamW:
             self.step.add_(1.0)
         if not self.norm_ready:
             if self.norm_table is not None:
-                from . import _lib
-                _lib.check(_lib.load().fmmt_grad_handover(len(self.grads), self.norm_blocks, self.norm_table.data_ptr(), self.norm_partial.data_ptr(),
-                                                          self.norm.data_ptr(), torch.cuda.current_stream(self.norm.device).cuda_stream), "fmmt_grad_handover(norm)")
+                ops.grad_handover_raw(len(self.grads), self.norm_blocks, self.norm_table, self.norm_partial, self.norm)
             else:
                 self.norm.copy_(torch.nn.utils.get_total_norm(self.grads, 2.0, foreach=True))
         self.norm_ready = False

@@ -35,6 +35,20 @@ CASES = [(96, 2, 14, 0, False), (96, 2, 14, 3, True), (96, 1, 56, 3, False), (96
 
 @pytest.mark.parametrize("C,n_img,H,shift,use_rs", CASES)
 def test_fused_block_half_forward_and_gradients(dev, C, n_img, H, shift, use_rs, monkeypatch):
+    _block_half_case(dev, C, n_img, H, shift, use_rs, monkeypatch)
+
+
+@pytest.mark.parametrize("n_img,H,shift", [(1, 7, 0), (1, 14, 3)])       # a single window; the smallest shifted grid (mask argument, `add` operand)
+@pytest.mark.parametrize("bwd,lnbwd", [(True, True), (False, True), (True, False)])
+def test_fused_block_half_backward_branches(dev, n_img, H, shift, bwd, lnbwd, monkeypatch):
+    """the same case with the backward's two switches off in turn: ops._WBLOCK_BWD False -- qkv re-computed with a GEMM, then
+    fmmt_window_attn_bwd -- and ops._WBLOCK_LNBWD False -- d(LN out) GEMM, then fmmt_layernorm_bwd with the residual gradient as `add`"""
+    monkeypatch.setattr(ops, "_WBLOCK_BWD", bwd)
+    monkeypatch.setattr(ops, "_WBLOCK_LNBWD", lnbwd)
+    _block_half_case(dev, 96, n_img, H, shift, False, monkeypatch)
+
+
+def _block_half_case(dev, C, n_img, H, shift, use_rs, monkeypatch):
     import support_wblock_cases as W
     nh = C // 32
     monkeypatch.setattr(ops, "_WBLOCK_WIDTHS", (96, 192))
@@ -368,6 +382,18 @@ def test_mlp_half_with_layernorm_prologue(dev, C, M, use_rs, monkeypatch):
     """fmmt_mlp_ln_fwd (norm2 -> Mlp -> DropPath -> residual in one launch) against fmmt_layernorm_fwd followed by fmmt_mlp_fwd, and
     both against fp64: forward, the saved LayerNorm output and statistics, every gradient; ragged last tile, dropped sample.
     (Both widths the fused kernels exist for: the model itself runs them at C = 96 only since round 6, ops._MLP_FUSED_WIDTHS.)"""
+    _mlp_half_case(dev, C, M, use_rs, monkeypatch)
+
+
+@pytest.mark.parametrize("bwd_ln", [True, False])
+def test_mlp_half_backward_with_and_without_the_layernorm_epilogue(dev, bwd_ln, monkeypatch):
+    """the same case at the fewest tokens that take the fused backward at all (M >= 4096 in ops.MlpLnFn.backward), with ops._MLP_BWD_LN on
+    (fmmt_mlp_ln_bwd_input) and off (fmmt_mlp_bwd_input, then fmmt_layernorm_bwd with the residual gradient as `add`)"""
+    monkeypatch.setattr(ops, "_MLP_BWD_LN", bwd_ln)
+    _mlp_half_case(dev, 96, 4096, True, monkeypatch)
+
+
+def _mlp_half_case(dev, C, M, use_rs, monkeypatch):
     import support_wblock_cases as W
     monkeypatch.setattr(ops, "_MLP_FUSED_WIDTHS", (96, 192))
     x = W.rnd("x", (M, C), 21, dtype=torch.bfloat16).requires_grad_(True)
