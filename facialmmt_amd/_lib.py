@@ -162,6 +162,16 @@ AUG_SIGNATURES = {
 # the record layout (include/fmmt_aug.h FMMT_AUG_*): words 0-7 a jitter record, 8 flags, 9-11 blur r / ww / fw, 12-15 top / left / h / w, 16-17 noise key
 AUG_WORDS, AUG_FLAG_GRAY, AUG_MAX_RADIUS, AUG_HALO = 20, 1, 1, 6
 
+# include/fmmt_groups.h, one to one: an eleventh table and header -- fmmt_adamw_batch and its guarded twin with the learning rate, betas, eps and
+# weight decay read per record from a group table (tests/test_param_groups_cpu.py holds table, header and library together)
+GROUPS_SIGNATURES = {
+    "fmmt_adamw_groups": (_i, [_i, _i, _p, _i, _p, _p, _p, _p, _f, _i, _p]),
+    "fmmt_adamw_groups_guarded": (_i, [_i, _i, _p, _i, _p, _p, _p, _p, _f, _i, _p]),
+}
+# the group record (include/fmmt_groups.h fmmt_adamw_group): the one place Python states it; train_step.FusedClipAdamW builds tables through this
+ADAMW_GROUP_BYTES = 32
+ADAMW_GROUP_FIELDS = [("lr", "<u8"), ("beta1", "<f4"), ("beta2", "<f4"), ("eps", "<f4"), ("weight_decay", "<f4"), ("pad", "<u4", (2,))]
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -182,7 +192,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

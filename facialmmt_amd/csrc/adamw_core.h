@@ -1,6 +1,7 @@
-// Clip + AdamW + bf16 twins over a descriptor table: the body of adamw_batch_kernel (misc.hip, fmmt_adamw_batch) and of
-// adamw_batch_guarded_kernel (guard.hip, fmmt_adamw_batch_guarded) -- ONE statement of the arithmetic, so that the guarded update on a finite
-// norm gives the bits of the plain one.  The kernels differ only in where `t` and the decision to run at all come from; the formulas and the
+// Clip + AdamW + bf16 twins over a descriptor table: the body of adamw_batch_kernel (misc.hip, fmmt_adamw_batch), of adamw_batch_guarded_kernel
+// (guard.hip, fmmt_adamw_batch_guarded) and of the two kernels of adamw_groups.hip (fmmt_adamw_groups, fmmt_adamw_groups_guarded) -- ONE statement
+// of the arithmetic, so that the guarded update on a finite norm gives the bits of the plain one and the grouped update the bits of one plain
+// launch per group.  The kernels differ only in where `t`, the hyper-parameters and the decision to run at all come from; the formulas and the
 // descriptor record are described above adamw_batch_kernel and in include/fmmt.h.
 #pragma once
 #include "fmmt_common.h"
@@ -13,21 +14,34 @@ struct AdamDesc {
     int blk_begin, g_bf16;                                      // g_bf16: the gradient is bf16 (the twin's own .grad), else fp32
 };
 
-// One block = 4096 elements of one record.  STEP_IS_BEFORE: *step_p is the update count BEFORE this update (the guarded kernel, whose step word
-// another kernel advances behind it), t = *step_p + 1; else *step_p is t itself.  coef = min(1, max_norm / (total_norm + 1e-6)) is
-// torch.nn.utils.clip_grad_norm_'s.
-template <bool STEP_IS_BEFORE>
-__device__ __forceinline__ void adamw_batch_body(const AdamDesc* __restrict__ desc, int n_desc, const float* __restrict__ lr_p,
-                                                 const float* __restrict__ step_p, const float* __restrict__ norm_p,
-                                                 float beta1, float beta2, float eps, float wd, float max_norm, int hf) {
+// what one record is stepped with: launch arguments in the one-group kernels, groups[group_of[record]] in the grouped ones -- block-uniform either way
+struct AdamHyper {
+    float lr, beta1, beta2, eps, wd;
+};
+
+// NaN and +-inf have every exponent bit set: a test on the bits, which no floating-point compiler option can fold away (the guarded kernels'
+// decision, and fmmt_guard_commit's behind them)
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// the record block `blockIdx.x` belongs to: the last one whose blk_begin is not behind it
+__device__ __forceinline__ int adamw_find_record(const AdamDesc* __restrict__ desc, int n_desc) {
     int lo = 0, hi = n_desc - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
         if (desc[mid].blk_begin <= (int)blockIdx.x) lo = mid;
         else hi = mid - 1;
     }
-    const AdamDesc d = desc[lo];
-    const float lr = *lr_p, t = STEP_IS_BEFORE ? *step_p + 1.0f : *step_p;
+    return lo;
+}
+
+// One block = 4096 elements of one record.  STEP_IS_BEFORE: *step_p is the update count BEFORE this update (the guarded kernel, whose step word
+// another kernel advances behind it), t = *step_p + 1; else *step_p is t itself.  coef = min(1, max_norm / (total_norm + 1e-6)) is
+// torch.nn.utils.clip_grad_norm_'s.
+template <bool STEP_IS_BEFORE>
+__device__ __forceinline__ void adamw_batch_body(const AdamDesc d, const AdamHyper h, const float* __restrict__ step_p,
+                                                 const float* __restrict__ norm_p, float max_norm, int hf) {
+    const float lr = h.lr, beta1 = h.beta1, beta2 = h.beta2, eps = h.eps, wd = h.wd;
+    const float t = STEP_IS_BEFORE ? *step_p + 1.0f : *step_p;
     const float coef = norm_p ? fminf(1.0f, max_norm / (*norm_p + 1e-6f)) : 1.0f;
     const float bc1 = 1.0f - powf(beta1, t), bc2s = sqrtf(1.0f - powf(beta2, t));
     const float step_size = hf ? lr * bc2s / bc1 : lr / bc1, decay = hf ? 1.0f : 1.0f - lr * wd;

@@ -14,14 +14,12 @@
 
 namespace {
 
-// NaN and +-inf have every exponent bit set: a test on the bits, which no floating-point compiler option can fold away
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 __global__ __launch_bounds__(256) void adamw_batch_guarded_kernel(const AdamDesc* __restrict__ desc, int n_desc, const float* __restrict__ lr_p,
                                                                   const float* __restrict__ step_p, const float* __restrict__ norm_p,
                                                                   float beta1, float beta2, float eps, float wd, float max_norm, int hf) {
     if (!finite_bits(*norm_p)) return;                       // block-uniform: nothing of p, m, v or the twins is read or written
-    adamw_batch_body<true>(desc, n_desc, lr_p, step_p, norm_p, beta1, beta2, eps, wd, max_norm, hf);
+    const int r = adamw_find_record(desc, n_desc);
+    adamw_batch_body<true>(desc[r], AdamHyper{*lr_p, beta1, beta2, eps, wd}, step_p, norm_p, max_norm, hf);
 }
 
 __global__ __launch_bounds__(64) void guard_commit_kernel(const float* __restrict__ norm_p, float* __restrict__ step, long long* __restrict__ words) {

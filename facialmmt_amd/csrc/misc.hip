@@ -302,11 +302,12 @@ __global__ __launch_bounds__(1024) void sumsq_finish_kernel(const float* __restr
     if (threadIdx.x == 0) out[0] = sqrtf(red[0]);
 }
 
-// the record (AdamDesc) and the body live in adamw_core.h, shared with the guarded update of guard.hip
+// the record (AdamDesc) and the body live in adamw_core.h, shared with the guarded update of guard.hip and the grouped ones of adamw_groups.hip
 __global__ __launch_bounds__(256) void adamw_batch_kernel(const AdamDesc* __restrict__ desc, int n_desc, const float* __restrict__ lr_p,
                                                           const float* __restrict__ step_p, const float* __restrict__ norm_p,
                                                           float beta1, float beta2, float eps, float wd, float max_norm, int hf) {
-    adamw_batch_body<false>(desc, n_desc, lr_p, step_p, norm_p, beta1, beta2, eps, wd, max_norm, hf);
+    const int r = adamw_find_record(desc, n_desc);
+    adamw_batch_body<false>(desc[r], AdamHyper{*lr_p, beta1, beta2, eps, wd}, step_p, norm_p, max_norm, hf);
 }
 
 // LayerNorm backward for a bf16 module with bf16 affine parameters (the text encoder's 49 LayerNorms: torch's own backward is

@@ -365,6 +365,33 @@ def adamw_batch_guarded(n, blocks, desc, lr, step, total_norm, beta1, beta2, eps
                                                float(weight_decay), float(max_norm), 1 if hf else 0, _st()), "fmmt_adamw_batch_guarded")
 
 
+def _group_tables(n, n_groups, group_of, groups, what):
+    if group_of.dtype != torch.int32 or not group_of.is_contiguous() or group_of.numel() != n:
+        raise ValueError(f"{what}: group_of is a contiguous int32 tensor with one entry per descriptor record ({n})")
+    if groups.dtype != torch.uint8 or not groups.is_contiguous() or groups.numel() != n_groups * _lib.ADAMW_GROUP_BYTES or n_groups < 1:
+        raise ValueError(f"{what}: groups is a contiguous uint8 tensor of n_groups >= 1 records of {_lib.ADAMW_GROUP_BYTES} bytes (include/fmmt_groups.h)")
+    return _p(group_of), _p(groups)
+
+
+def adamw_groups(n, blocks, desc, n_groups, group_of, groups, step, total_norm, max_norm, hf=False):
+    """fmmt_adamw_groups: adamw_batch with lr / betas / eps / weight decay per record -- record i is stepped with groups[group_of[i]] (`groups`:
+    n_groups records of _lib.ADAMW_GROUP_FIELDS as a uint8 device tensor, `group_of`: int32, one per record, every entry in [0, n_groups): the
+    caller's to check, train_step.group_plan does); one step word, one norm word and one max_norm for all groups"""
+    go, gr = _group_tables(n, n_groups, group_of, groups, "adamw_groups")
+    check(_lib.load().fmmt_adamw_groups(n, blocks, _p(desc), n_groups, go, gr, _p(step), _p(total_norm), float(max_norm), 1 if hf else 0, _st()),
+          "fmmt_adamw_groups")
+
+
+def adamw_groups_guarded(n, blocks, desc, n_groups, group_of, groups, step, total_norm, max_norm, hf=False):
+    """fmmt_adamw_groups_guarded: adamw_groups that touches nothing when `total_norm` (required) holds a NaN or an inf; `step` is the update count
+    BEFORE this update and is only read -- guard_commit, behind it on the same stream, advances it (as adamw_batch_guarded to adamw_batch)"""
+    if total_norm is None:
+        raise ValueError("adamw_groups_guarded: total_norm is what the guard decides on; it cannot be None")
+    go, gr = _group_tables(n, n_groups, group_of, groups, "adamw_groups_guarded")
+    check(_lib.load().fmmt_adamw_groups_guarded(n, blocks, _p(desc), n_groups, go, gr, _p(step), _p(total_norm), float(max_norm), 1 if hf else 0,
+                                                _st()), "fmmt_adamw_groups_guarded")
+
+
 def grad_handover_raw(n, blocks, table, partial, norm_out):
     """fmmt_grad_handover over a device table of `n` records (train_step.FusedHandOver's layout; `blocks` blocks of 4096 elements, one fp32 word
     of `partial` each): every gradient into its fp32 slot and the norm of all of them into `norm_out`, on the current stream of the table's device"""

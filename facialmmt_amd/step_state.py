@@ -138,7 +138,9 @@ def check_optimizer_state(sd, opt, who="load_state_dict", fused=None):
         raise RuntimeError(f"{who}: an optimizer state holds 'state' and 'param_groups'")
     if len(sd["param_groups"]) != len(opt.param_groups):
         raise RuntimeError(f"{who}: {len(sd['param_groups'])} parameter groups loaded, the optimizer has {len(opt.param_groups)}")
-    for gs, g in zip(sd["param_groups"], opt.param_groups):
+    caller = who
+    for j, (gs, g) in enumerate(zip(sd["param_groups"], opt.param_groups)):
+        who = f"{caller}, group {j}" if len(opt.param_groups) > 1 else caller      # several groups: every message below names its group
         if len(gs["params"]) != len(g["params"]):
             raise RuntimeError(f"{who}: the loaded optimizer state is for {len(gs['params'])} parameters, the optimizer steps {len(g['params'])}")
         other = set(gs).symmetric_difference(g) - set(_GROUP_FREE)
@@ -163,7 +165,7 @@ def check_optimizer_state(sd, opt, who="load_state_dict", fused=None):
             raise ValueError(f"{who}: per-parameter step counters of one group disagree: {sorted(counts)}")
         every |= counts
     if fused is not None and len(every) > 1:
-        raise ValueError(f"{who}: per-parameter step counters disagree: {sorted(every)}; the fused update keeps one counter for all parameters")
+        raise ValueError(f"{caller}: per-parameter step counters disagree: {sorted(every)}; the fused update keeps one counter for all parameters of all groups")
 
 
 def _place(k, t, p, group):

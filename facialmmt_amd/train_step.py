@@ -850,6 +850,59 @@ def step_parameters(mm, masters=None):
     return [master_of.get(id(p), p) for p in mm.parameters() if p.requires_grad]
 
 
+def named_step_parameters(mm, masters=None):
+    """(name, parameter) for every parameter of step_parameters(mm, masters), in its order: the name is mm.named_parameters()'s, the parameter
+    the one the optimizer steps (the fp32 master of a bf16 text-encoder weight) -- what parameter groups are built from by name:
+        decay = [p for n, p in named_step_parameters(mm, masters) if not ("bias" in n or "LayerNorm" in n)]"""
+    master_of = {id(l): m for l, m in masters.pairs()} if masters is not None else {}
+    for name, p in mm.named_parameters():
+        if p.requires_grad:
+            yield name, master_of.get(id(p), p)
+
+
+_GROUPS_AGREE_ON = (("correct_bias", True), ("amsgrad", False), ("maximize", False))
+
+
+def group_plan(opt, params):
+    """The host half of the grouped fused update, pure (CPU tensors do): which group of `opt` steps each parameter of `params`, and with what.
+    Returns a namespace: `group_of`, one index into opt.param_groups per parameter, in `params`' order (the order of FusedClipAdamW's descriptor
+    table); `groups`, one dict per group of the optimizer with its `lr` (as the group holds it: a tensor or a float), `betas`, `eps` and
+    `weight_decay`.  A parameter of the optimizer that is not in `params` is ignored (the eager optimizer skips a parameter without a gradient);
+    ValueError for a parameter of `params` that no group holds, and for groups that disagree on correct_bias, amsgrad or maximize (one launch
+    has one hf_semantics and one formula)."""
+    if not opt.param_groups:
+        raise ValueError("group_plan: the optimizer has no parameter group")
+    for key, default in _GROUPS_AGREE_ON:
+        seen = [bool(g.get(key, default)) for g in opt.param_groups]
+        if len(set(seen)) > 1:
+            raise ValueError(f"group_plan: the parameter groups disagree on `{key}` ({seen}); the fused update takes one value for all groups")
+    at = {id(p): j for j, g in enumerate(opt.param_groups) for p in g["params"]}
+    group_of = []
+    for i, p in enumerate(params):
+        if id(p) not in at:
+            raise ValueError(f"group_plan: parameter {i} of `params` (shape {tuple(p.shape)}) is in no parameter group of the optimizer")
+        group_of.append(at[id(p)])
+    groups = [{"lr": g["lr"], "betas": tuple(float(b) for b in g["betas"]), "eps": float(g["eps"]), "weight_decay": float(g["weight_decay"])}
+              for g in opt.param_groups]
+    return types.SimpleNamespace(group_of=group_of, groups=groups)
+
+
+def group_tables(plan, dev):
+    """the device half of group_plan: (`group_of` as int32, the group table of include/fmmt_groups.h as uint8) for ops.adamw_groups; every group's
+    `lr` must be an fp32 tensor on `dev` -- the table holds its ADDRESS, so a scheduler that fills the tensor in place reaches the kernel"""
+    import numpy as np
+    from . import _lib
+    tab = np.zeros(len(plan.groups), dtype=np.dtype(_lib.ADAMW_GROUP_FIELDS))
+    assert tab.itemsize == _lib.ADAMW_GROUP_BYTES
+    for j, h in enumerate(plan.groups):
+        if not (torch.is_tensor(h["lr"]) and h["lr"].dtype == torch.float32 and h["lr"].numel() == 1 and h["lr"].device == dev):
+            raise ValueError(f"group_tables: the learning rate of group {j} is not one fp32 word on {dev}")
+        tab[j] = (h["lr"].data_ptr(), h["betas"][0], h["betas"][1], h["eps"], h["weight_decay"], 0)
+    if any(not 0 <= j < len(plan.groups) for j in plan.group_of):
+        raise ValueError("group_tables: a group index outside the group table")
+    return torch.tensor(plan.group_of, dtype=torch.int32).to(dev), torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
+
+
 class HFAdamW(torch.optim.Optimizer):
     """`transformers.AdamW` restated (the optimizer class the reference constructs, train.py:307,333; transformers 4.24
     optimization.py, not vendored under the reference tree): defaults betas (0.9, 0.999), **eps 1e-6, weight_decay 0.0**,
@@ -858,7 +911,7 @@ class HFAdamW(torch.optim.Optimizer):
     i.e. eps is added BEFORE the bias correction and the decoupled decay is applied AFTER the update -- both differ from
     torch.optim.AdamW (whose defaults are also eps 1e-8, weight_decay 0.01).  `lr` may be a 0-dim device tensor and the step
     counter is a device tensor, so the eager step is capture-safe; the graphed steps hand the same hyper-parameters to
-    fmmt_adamw_batch(hf_semantics=1) through FusedClipAdamW.  One parameter group."""
+    fmmt_adamw_batch(hf_semantics=1) through FusedClipAdamW (several parameter groups: fmmt_adamw_groups).  Every group has its own counter here."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias))
@@ -1057,27 +1110,41 @@ class FusedClipAdamW:
     """clip_grad_norm_ + AdamW.step() (torch.optim.AdamW, or HFAdamW = the reference's transformers.AdamW) (+ the bf16 re-rounding of parameters stepped through fp32 masters) as one
     multi-tensor norm and ONE kernel launch (fmmt_adamw_batch): the gradients are read once and not scaled in place, the fp32
     parameters are not read a second time for their bf16 twins.  Takes its hyper-parameters from an existing torch AdamW
-    (one parameter group, tensor learning rate on the device as `capturable=True` keeps it, so a LambdaLR scheduler keeps
+    (tensor learning rate on the device as `capturable=True` keeps it, so a LambdaLR scheduler keeps
     working); keeps its own moments and step counter -- `optimizer.state` stays empty while this is in use.
+    Parameter groups: with one group the launch is fmmt_adamw_batch and the group's betas / eps / weight decay are launch arguments; with several
+    (no decay on biases and LayerNorm weights, a learning rate per sub-model, a group held still with lr = 0) it is fmmt_adamw_groups -- still ONE
+    launch, which reads each record's learning rate word, betas, eps and weight decay from a group table built here once (group_plan).  One update
+    count and one clip coefficient serve all groups, as clip_grad_norm_(model.parameters()) and a step() over all groups give.
     `monitor` (a TrainMonitor; None: the path above, unchanged): the update is SKIPPED when the gradient norm is NaN or infinite -- what GradScaler
     does for the reference under AMP (train.py:139-143) -- decided on the device: update() runs the norm, ops.adamw_batch_guarded (every block
     reads the norm first and leaves p, m, v and the bf16 twins alone when it is not finite) and ops.guard_commit (advances `step` only for an
     applied update, counts applied / skipped in the monitor).  `step` stays the number of APPLIED updates, so export() / load_from() mean what
     they meant; with finite gradients every bit is the unguarded path's."""
 
+    plan = group_of = group_table = None                     # several parameter groups only: group_plan's result and its two device tables
+
     @staticmethod
     def eligible(opt, params):
-        if not FUSED_ADAMW or type(opt) not in (torch.optim.AdamW, HFAdamW) or len(opt.param_groups) != 1:
+        """any number of parameter groups (at least one) of torch.optim.AdamW / HFAdamW, each with one fp32 word on the device as its learning rate (one tensor
+        may serve several groups), no amsgrad, no maximize, correct_bias; fp32 device parameters, each held by a group"""
+        if not FUSED_ADAMW or type(opt) not in (torch.optim.AdamW, HFAdamW) or len(opt.param_groups) < 1:
             return False
-        g = opt.param_groups[0]
-        return (torch.is_tensor(g["lr"]) and g["lr"].is_cuda and not g.get("amsgrad", False) and not g.get("maximize", False)
-                and g.get("correct_bias", True) and all(p.dtype == torch.float32 and p.is_cuda for p in params))
+        for g in opt.param_groups:
+            if not (torch.is_tensor(g["lr"]) and g["lr"].is_cuda and g["lr"].numel() == 1 and g["lr"].dtype == torch.float32 and not g.get("amsgrad", False)
+                    and not g.get("maximize", False) and g.get("correct_bias", True)):
+                return False
+        held = {id(p) for g in opt.param_groups for p in g["params"]} if len(opt.param_groups) > 1 else None
+        return all(p.dtype == torch.float32 and p.is_cuda and (held is None or id(p) in held) for p in params)
 
     def __init__(self, opt, params, grad_of, low_of, max_norm, monitor=None):
         import numpy as np
         self.monitor = monitor
-        g = opt.param_groups[0]
-        self.lr, (self.b1, self.b2), self.eps, self.wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        if len(opt.param_groups) == 1:                       # the hyper-parameters are launch arguments of fmmt_adamw_batch, as ever
+            g = opt.param_groups[0]
+            self.lr, (self.b1, self.b2), self.eps, self.wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        else:                                                # fmmt_adamw_groups reads them from two device tables, built below
+            self.plan = group_plan(opt, params)
         self.hf = isinstance(opt, HFAdamW)                    # transformers.AdamW's update (the reference's class) vs torch.optim.AdamW's
         self.max_norm = float(max_norm)
         dev = params[0].device
@@ -1112,6 +1179,8 @@ class FusedClipAdamW:
         self.desc = torch.from_numpy(arr.view(np.uint8).copy()).to(dev)
         self.n, self.blocks = len(recs), blocks
         self._digest_partial = None
+        if self.plan is not None:                            # built once: the learning rates are addresses, the schedulers write through them
+            self.group_of, self.group_table = group_tables(self.plan, dev)
 
     def digest(self, out=None):
         """the replica digest of what this object steps (ops.param_digest on its own descriptor table): six int64 words on the device -- (S1, S2)
@@ -1131,11 +1200,29 @@ class FusedClipAdamW:
     def load_from(self, opt):
         """take moments and step counter from `opt` (after HFAdamW.load_hf_state_dict / Optimizer.load_state_dict of a checkpoint): this object
         keeps its own m, v and step -- the ones the captured update addresses -- so a loaded optimizer state must be copied IN, in place.
-        Parameters the optimizer holds no state for keep zero moments.  The loaded group's betas / eps / weight decay must be this object's:
-        the captured update holds them as launch arguments, so others cannot take effect -- ValueError, nothing copied."""
+        Parameters the optimizer holds no state for keep zero moments.  Every loaded group's betas / eps / weight decay must be this object's
+        for that group: the captured update holds them as launch arguments (several groups: in its group table), so others cannot take effect;
+        and the groups must agree on the update count, for there is one counter -- ValueError naming the group and the field, nothing copied."""
         params = self.keep[0]
-        g = opt.param_groups[0]
-        step_state.check_hyper(g, {"betas": (self.b1, self.b2), "eps": self.eps, "weight_decay": self.wd}, "FusedClipAdamW.load_from")
+        plan = self.plan
+        hyper = plan.groups if plan is not None else [{"betas": (self.b1, self.b2), "eps": self.eps, "weight_decay": self.wd}]
+        group_of = plan.group_of if plan is not None else [0] * len(params)
+        if len(opt.param_groups) != len(hyper):
+            raise ValueError(f"FusedClipAdamW.load_from: {len(opt.param_groups)} parameter groups loaded, the update was built over {len(hyper)}")
+        for j, (g, h) in enumerate(zip(opt.param_groups, hyper)):
+            who = "FusedClipAdamW.load_from" if plan is None else f"FusedClipAdamW.load_from, group {j}"
+            step_state.check_hyper(g, {k: h[k] for k in ("betas", "eps", "weight_decay")}, who)
+        counts = {}                                           # group -> its update count: the group's own counter (HFAdamW), else its parameters'
+        for j in sorted(set(group_of)):
+            t = opt.param_groups[j].get("step")
+            ts = {float(t)} if t is not None else {float(opt.state[p]["step"]) for p, k in zip(params, group_of)
+                                                   if k == j and p in opt.state and "step" in opt.state[p]}
+            if len(ts) > 1:
+                raise ValueError(f"per-parameter step counters disagree: {sorted(ts)}")
+            counts[j] = ts.pop() if ts else None
+        seen = {t for t in counts.values() if t is not None}
+        if len(seen) > 1:
+            raise ValueError(f"FusedClipAdamW.load_from: the groups' step counters disagree ({counts}); the fused update keeps one counter for all groups")
         for p, m, v in zip(params, self.m, self.v):
             st = opt.state.get(p, {})
             if "exp_avg" in st:
@@ -1144,13 +1231,7 @@ class FusedClipAdamW:
             else:
                 m.zero_()
                 v.zero_()
-        t = g.get("step")
-        if t is None:                                         # torch.optim.AdamW: a per-parameter counter
-            ts = {float(opt.state[p]["step"]) for p in params if p in opt.state and "step" in opt.state[p]}
-            if len(ts) > 1:
-                raise ValueError(f"per-parameter step counters disagree: {sorted(ts)}")
-            t = ts.pop() if ts else 0.0
-        self.step.fill_(float(t))
+        self.step.fill_(seen.pop() if seen else 0.0)
 
     @torch.no_grad()
     def export(self, params=None):
@@ -1171,6 +1252,14 @@ class FusedClipAdamW:
             else:
                 self.norm.copy_(torch.nn.utils.get_total_norm(self.grads, 2.0, foreach=True))
         self.norm_ready = False
+        if self.group_table is not None:                      # several groups: the same two launches, hyper-parameters from the group table
+            n_groups = len(self.plan.groups)
+            if self.monitor is not None:
+                ops.adamw_groups_guarded(self.n, self.blocks, self.desc, n_groups, self.group_of, self.group_table, self.step, self.norm, self.max_norm, self.hf)
+                ops.guard_commit(self.norm, self.step, self.monitor.words)
+                return
+            ops.adamw_groups(self.n, self.blocks, self.desc, n_groups, self.group_of, self.group_table, self.step, self.norm, self.max_norm, self.hf)
+            return
         if self.monitor is not None:                          # `step` is the count before this update; the commit advances it when the update ran
             ops.adamw_batch_guarded(self.n, self.blocks, self.desc, self.lr, self.step, self.norm, self.b1, self.b2, self.eps, self.wd, self.max_norm, self.hf)
             ops.guard_commit(self.norm, self.step, self.monitor.words)
@@ -1209,8 +1298,8 @@ class FlatGradientTail:
         if not isinstance(flat, GradientAverager):
             flat = list(flat)
         if monitor is not None and not FusedClipAdamW.eligible(opt, flat.params if isinstance(flat, GradientAverager) else flat):
-            raise ValueError("skip_nonfinite needs the fused update (FusedClipAdamW.eligible: one group of torch.optim.AdamW / HFAdamW with a device "
-                             "learning rate over fp32 device parameters): the stock optimizer path cannot skip an update without a host synchronisation")
+            raise ValueError("skip_nonfinite needs the fused update (FusedClipAdamW.eligible: torch.optim.AdamW / HFAdamW whose parameter groups all hold a "
+                             "device learning rate, over fp32 device parameters): the stock optimizer path cannot skip an update without a host synchronisation")
         self.monitor = monitor
         self.opt, self.clip, self.accumulate, self.masters, self.exchanging = opt, clip, bool(accumulate), masters, bool(exchanging)
         self.flat = flat if isinstance(flat, GradientAverager) else GradientAverager(flat, hooks=False)
@@ -1256,8 +1345,8 @@ class FlatGradientTail:
         """FusedClipAdamW.digest() of the parameters and moments this tail steps (compare across ranks: parallel.replicas_agree); only with the
         fused update, which owns the descriptor table -- ValueError otherwise, as skip_nonfinite"""
         if self.fused is None:
-            raise ValueError("replica_digest needs the fused update (FusedClipAdamW.eligible: one group of torch.optim.AdamW / HFAdamW with a device "
-                             "learning rate over fp32 device parameters): the digest runs over its descriptor table")
+            raise ValueError("replica_digest needs the fused update (FusedClipAdamW.eligible: torch.optim.AdamW / HFAdamW whose parameter groups all hold a "
+                             "device learning rate, over fp32 device parameters): the digest runs over its descriptor table")
         return self.fused.digest()
 
     def undo_warmup(self):

@@ -531,6 +531,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_jitter.h"
 /* The Aff-Wild2 training augmentation of the auxiliary task inside the uint8 pre-step (grayscale, ColorJitter, Gaussian blur, RandomErasing): likewise, held to _lib.AUG_SIGNATURES. */
 #include "fmmt_aug.h"
+/* Clip + AdamW over parameter groups, learning rate / betas / eps / weight decay per record (fmmt_adamw_groups, fmmt_adamw_groups_guarded): likewise, held to _lib.GROUPS_SIGNATURES. */
+#include "fmmt_groups.h"
 
 #ifdef __cplusplus
 }
