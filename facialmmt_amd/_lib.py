@@ -172,6 +172,16 @@ GROUPS_SIGNATURES = {
 ADAMW_GROUP_BYTES = 32
 ADAMW_GROUP_FIELDS = [("lr", "<u8"), ("beta1", "<f4"), ("beta2", "<f4"), ("eps", "<f4"), ("weight_decay", "<f4"), ("pad", "<u4", (2,))]
 
+# include/fmmt_stats.h, one to one: a twelfth table and header -- per-record statistics of one field of fmmt_adamw_batch's descriptor table and the
+# snapshot of a bad update (tests/test_grad_report_cpu.py holds table, header and library together)
+STATS_SIGNATURES = {
+    "fmmt_table_stats": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+}
+# the field selector and the 16-byte record (include/fmmt_stats.h FMMT_STATS_*): the one place Python states them; train_step.GradReport reads through these
+STATS_G, STATS_P, STATS_M, STATS_V = 0, 1, 2, 3
+STATS_BYTES, STATS_BAD_WORDS = 16, 2
+STATS_FIELDS = [("sumsq", "<f4"), ("max_abs", "<f4"), ("nonfinite", "<i4"), ("reserved", "<i4")]
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -192,7 +202,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

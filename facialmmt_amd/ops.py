@@ -437,6 +437,30 @@ def param_digest(n, blocks, desc, out=None, partial=None):
     return out
 
 
+def _stats_rows(t, rows, what):
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 4 or t.shape[0] < rows:
+        raise ValueError(f"table_stats: {what} is a contiguous int32 tensor of at least {rows} rows of four words (include/fmmt_stats.h)")
+    return _p(t)
+
+
+def table_stats(which, n, blocks, desc, partial, stats, norm=None, bad_stats=None, bad_words=None):
+    """fmmt_table_stats over adamw_batch's descriptor table (`n` records, `blocks` blocks of 4096 elements): per record the fp32 sum of squares,
+    the largest magnitude that is not a NaN and the count of NaN / inf elements of field `which` (_lib.STATS_G / _P / _M / _V) into `stats`, (n, 4)
+    int32 rows of _lib.STATS_FIELDS; `partial`: (blocks, 4) int32 rows of scratch.  `norm` (one fp32 device word, the one the guarded update reads):
+    when it holds a NaN or an inf, `stats` is also copied into `bad_stats` (as `stats`), `bad_words[0]` (int64, two words) counts the bad update
+    and `bad_words[1]` names the first record with a non-finite element or sum, -1 for none.  Two launches on the current stream, no atomics,
+    capture-safe; train_step.GradReport owns the buffers."""
+    if norm is None and (bad_stats is not None or bad_words is not None):
+        raise ValueError("table_stats: bad_stats / bad_words are written on a non-finite `norm`; they cannot be given without it")
+    if norm is not None and (norm.dtype != torch.float32 or norm.numel() != 1):
+        raise ValueError("table_stats: norm is one float32 value on the device")
+    if bad_words is not None and (bad_words.dtype != torch.int64 or not bad_words.is_contiguous() or bad_words.numel() != _lib.STATS_BAD_WORDS):
+        raise ValueError(f"table_stats: bad_words is a contiguous int64 tensor of {_lib.STATS_BAD_WORDS} entries")
+    check(_lib.load().fmmt_table_stats(int(which), n, blocks, _p(desc), _stats_rows(partial, blocks, "partial"), _stats_rows(stats, n, "stats"), _p(norm),
+                                       None if bad_stats is None else _stats_rows(bad_stats, n, "bad_stats"), _p(bad_words), _st()), "fmmt_table_stats")
+    return stats
+
+
 class VendorLinearFn(torch.autograd.Function):
     """y = x W^T + b with the vendor library's GEMMs (torch.nn.functional.linear / matmul) and fmmt_colsum for the bias gradient:
     the text encoder's Linear layers (few thousand tokens: hipBLASLt's ground; its autograd formula spends a memset and a

@@ -1106,6 +1106,128 @@ class TrainMonitor:
         ops.monitor_loss(loss if loss.dtype == torch.float32 else loss.float(), scale, self.words)
 
 
+# REPORT_NOTE.  `grad_report=True` on a graphed training step (default False: no buffer, no launch, every bit as before): the step builds a GradReport
+# (`step.grad_report`) over the fused update's descriptor table, and every update runs ops.table_stats over the flat gradient buffers between the
+# clip norm and the update launch -- the values the update sees, before they are zeroed (train.py:135-143: the moment p.grad can be inspected in
+# the reference).  `step.grad_report.read()` gives each parameter's gradient norm, largest magnitude and NaN / inf count of the last update by
+# name; an update whose norm was NaN or infinite leaves a snapshot behind (`last_bad`, `last_bad.first`) that later clean updates do not touch.
+# With or without skip_nonfinite: without the guard the parameters still go NaN, but the snapshot names the cause.  Only with the fused update
+# (ValueError otherwise, as skip_nonfinite); a diagnostic, not part of state_dict().
+class GradReport:
+    """Per-parameter statistics of what the fused update reads, kept on the device: `stats` (one record of _lib.STATS_FIELDS per record of
+    FusedClipAdamW's descriptor table, written by every captured update), `bad_stats` / `bad_words` (the copy a non-finite norm leaves, its count
+    and the first offending record) and `partial` (the per-block scratch) -- include/fmmt_stats.h.  `read()` is one device-to-host copy;
+    `reset()` zeroes in place (the captured graphs keep these addresses); `state(which)` runs the kernel on demand over the parameters or a
+    moment.  `named`: (name, parameter) pairs, matched by identity to the table's order when FusedClipAdamW binds the report to its table (bind():
+    the buffers exist from then on); a parameter without a name is `param{i}`."""
+
+    def __init__(self, named=()):
+        self.named = [(name, p) for name, p in named]
+        self.names, self.n, self.blocks = [], 0, 0
+        self.desc = self.buf = self.stats = self.bad_stats = self.bad_words = self.partial = self._on_demand = None
+
+    def bind(self, desc, n, blocks, params):
+        """FusedClipAdamW's: the descriptor table this report is over (`n` records in `blocks` blocks, kept alive here too) and the parameters of its
+        records, in order"""
+        from . import _lib
+        if self.desc is not None:
+            raise RuntimeError("GradReport: already bound to an update's table; one report serves one FusedClipAdamW")
+        if len(params) != n:
+            raise ValueError(f"GradReport.bind: {len(params)} parameters for a table of {n} records")
+        name_of = {}
+        for name, p in self.named:
+            name_of.setdefault(id(p), name)
+        self.names = [name_of.get(id(p), f"param{i}") for i, p in enumerate(params)]
+        self.desc, self.n, self.blocks = desc, int(n), int(blocks)
+        # ONE allocation, so that read() is one copy: stats rows, bad_stats rows, then the two int64 words as one more 16-byte row
+        self.buf = torch.zeros((2 * n + 1, 4), dtype=torch.int32, device=desc.device)
+        self.stats, self.bad_stats = self.buf[:n], self.buf[n:2 * n]
+        self.bad_words = self.buf[2 * n].view(torch.int64)
+        assert self.bad_words.numel() == _lib.STATS_BAD_WORDS
+        self.partial = torch.empty((self.blocks, 4), dtype=torch.int32, device=desc.device)
+
+    def reset(self):
+        if self.buf is not None:
+            self.buf.zero_()
+
+    def record(self, norm):
+        """inside the update, behind the norm and in front of the update launch: two launches, capture-safe"""
+        from . import _lib, ops
+        ops.table_stats(_lib.STATS_G, self.n, self.blocks, self.desc, self.partial, self.stats, norm=norm, bad_stats=self.bad_stats, bad_words=self.bad_words)
+
+    @staticmethod
+    def _fields(rows, names):
+        import numpy as np
+        sumsq = rows["sumsq"].copy()
+        with np.errstate(invalid="ignore", over="ignore"):
+            norm, total = np.sqrt(sumsq), float(np.sqrt(sumsq.astype(np.float64).sum()))
+        ns = types.SimpleNamespace(names=list(names), norm=norm, sumsq=sumsq, max_abs=rows["max_abs"].copy(), nonfinite=rows["nonfinite"].copy(), total_norm=total)
+
+        def worst(k):
+            """the k names with the largest norm, largest first; a NaN norm counts as the largest of all"""
+            key = np.where(np.isnan(ns.norm), np.inf, ns.norm)
+            return [ns.names[i] for i in np.argsort(-key, kind="stable")[:max(int(k), 0)]]
+        ns.worst = worst
+        return ns
+
+    @staticmethod
+    def summarise(stats_host, bad_host, bad_words_host, names):
+        """the host half of read(), pure: `stats_host` / `bad_host` = the records as copied from the device ((n, 4) int32 rows, or None for
+        `bad_host` and `bad_words_host`: no snapshot fields), `bad_words_host` = the two int64 words.  Returns a namespace: names, norm (sqrt of
+        sumsq), sumsq, max_abs, nonfinite (numpy, one entry per name), total_norm (sqrt of the fp64 sum of sumsq), worst(k); and with the
+        snapshot: bad_updates, last_bad -- the same fields of the last update whose norm was not finite plus `first`, the name of the first
+        tensor with a non-finite element or sum (None when no single tensor has one); last_bad is None while bad_updates == 0"""
+        import numpy as np
+        from . import _lib
+        rec = np.dtype(_lib.STATS_FIELDS)
+        names = list(names)
+
+        def rows(host, what):
+            a = np.ascontiguousarray(host, dtype=np.int32)
+            if a.shape != (len(names), 4):
+                raise ValueError(f"GradReport.summarise: {what} is {len(names)} rows of four int32 words")
+            return a.view(rec).reshape(len(names))
+        out = GradReport._fields(rows(stats_host, "stats_host"), names)
+        if bad_words_host is None:
+            return out
+        words = np.ascontiguousarray(bad_words_host, dtype=np.int64)
+        if words.shape != (_lib.STATS_BAD_WORDS,):
+            raise ValueError(f"GradReport.summarise: {_lib.STATS_BAD_WORDS} int64 words")
+        out.bad_updates, out.last_bad = int(words[0]), None
+        if out.bad_updates:
+            first = int(words[1])
+            if not -1 <= first < len(names):
+                raise ValueError(f"GradReport.summarise: the first bad record is {first}, the table has {len(names)}")
+            out.last_bad = GradReport._fields(rows(bad_host, "bad_host"), names)
+            out.last_bad.first = names[first] if first >= 0 else None
+        return out
+
+    def read(self):
+        if self.desc is None:
+            raise RuntimeError("GradReport.read: the report is not bound to an update's table yet (FusedClipAdamW(report=...))")
+        host = self.buf.cpu().numpy()
+        n = self.n
+        return self.summarise(host[:n], host[n:2 * n], host[2 * n].view("<i8"), self.names)
+
+    def worst(self, k):
+        return self.read().worst(k)
+
+    def state(self, which):
+        """the same statistics of the parameters ("p"), first ("m") or second ("v") moments, now and not captured: after load_state_dict, or when
+        parallel.replicas_agree raised, to name the tensor.  Its own result rows: the captured update's are not touched; the per-block scratch is
+        shared with it, so call this on the stream the step is replayed on (the current one, as everything here), where the two are ordered"""
+        from . import _lib, ops
+        code = {"p": _lib.STATS_P, "m": _lib.STATS_M, "v": _lib.STATS_V}.get(which)
+        if code is None:
+            raise ValueError(f'GradReport.state: which is "p", "m" or "v", not {which!r}')
+        if self.desc is None:
+            raise RuntimeError("GradReport.state: the report is not bound to an update's table yet (FusedClipAdamW(report=...))")
+        if self._on_demand is None:
+            self._on_demand = torch.empty((self.n, 4), dtype=torch.int32, device=self.buf.device)
+        ops.table_stats(code, self.n, self.blocks, self.desc, self.partial, self._on_demand)
+        return self.summarise(self._on_demand.cpu().numpy(), None, None, self.names)
+
+
 class FusedClipAdamW:
     """clip_grad_norm_ + AdamW.step() (torch.optim.AdamW, or HFAdamW = the reference's transformers.AdamW) (+ the bf16 re-rounding of parameters stepped through fp32 masters) as one
     multi-tensor norm and ONE kernel launch (fmmt_adamw_batch): the gradients are read once and not scaled in place, the fp32
@@ -1120,7 +1242,10 @@ class FusedClipAdamW:
     does for the reference under AMP (train.py:139-143) -- decided on the device: update() runs the norm, ops.adamw_batch_guarded (every block
     reads the norm first and leaves p, m, v and the bf16 twins alone when it is not finite) and ops.guard_commit (advances `step` only for an
     applied update, counts applied / skipped in the monitor).  `step` stays the number of APPLIED updates, so export() / load_from() mean what
-    they meant; with finite gradients every bit is the unguarded path's."""
+    they meant; with finite gradients every bit is the unguarded path's.
+    `report` (a GradReport; None: no launch more): REPORT_NOTE -- update() runs ops.table_stats over the gradient field of the descriptor table behind
+    the norm (ready from the hand-over, or taken here over the reduced buffers) and in front of whichever of the four update launches runs, so the
+    report sees the values the update sees: on one rank or several, with or without accumulation, with one group or many."""
 
     plan = group_of = group_table = None                     # several parameter groups only: group_plan's result and its two device tables
 
@@ -1137,9 +1262,10 @@ class FusedClipAdamW:
         held = {id(p) for g in opt.param_groups for p in g["params"]} if len(opt.param_groups) > 1 else None
         return all(p.dtype == torch.float32 and p.is_cuda and (held is None or id(p) in held) for p in params)
 
-    def __init__(self, opt, params, grad_of, low_of, max_norm, monitor=None):
+    def __init__(self, opt, params, grad_of, low_of, max_norm, monitor=None, report=None):
         import numpy as np
         self.monitor = monitor
+        self.report = report
         if len(opt.param_groups) == 1:                       # the hyper-parameters are launch arguments of fmmt_adamw_batch, as ever
             g = opt.param_groups[0]
             self.lr, (self.b1, self.b2), self.eps, self.wd = g["lr"], g["betas"], g["eps"], g["weight_decay"]
@@ -1179,6 +1305,8 @@ class FusedClipAdamW:
         self.desc = torch.from_numpy(arr.view(np.uint8).copy()).to(dev)
         self.n, self.blocks = len(recs), blocks
         self._digest_partial = None
+        if report is not None:
+            report.bind(self.desc, self.n, self.blocks, params)
         if self.plan is not None:                            # built once: the learning rates are addresses, the schedulers write through them
             self.group_of, self.group_table = group_tables(self.plan, dev)
 
@@ -1252,6 +1380,8 @@ class FusedClipAdamW:
             else:
                 self.norm.copy_(torch.nn.utils.get_total_norm(self.grads, 2.0, foreach=True))
         self.norm_ready = False
+        if self.report is not None:                           # behind the norm, in front of the update: the values the update reads
+            self.report.record(self.norm)
         if self.group_table is not None:                      # several groups: the same two launches, hyper-parameters from the group table
             n_groups = len(self.plan.groups)
             if self.monitor is not None:
@@ -1291,12 +1421,17 @@ class FlatGradientTail:
     `monitor` (a TrainMonitor): the update is skipped on a non-finite gradient norm (FusedClipAdamW) -- only with the fused update: the stock
     clip_grad_norm_ + opt.step() path cannot decide without a host synchronisation, so an optimizer FusedClipAdamW.eligible rejects is a
     ValueError.  With accumulation a bad micro-step makes the window's buffers non-finite: the window's one update is skipped and update()
-    zeroes the buffers as always, so nothing of it reaches the next window."""
+    zeroes the buffers as always, so nothing of it reaches the next window.
+    `report` (a GradReport): REPORT_NOTE -- handed to FusedClipAdamW, whose table it reads; likewise a ValueError without the fused update."""
 
-    def __init__(self, flat, opt, clip, accumulate, masters=None, exchanging=False, capture_tables=4, monitor=None):
+    def __init__(self, flat, opt, clip, accumulate, masters=None, exchanging=False, capture_tables=4, monitor=None, report=None):
         from .parallel import GradientAverager
         if not isinstance(flat, GradientAverager):
             flat = list(flat)
+        if report is not None and not FusedClipAdamW.eligible(opt, flat.params if isinstance(flat, GradientAverager) else flat):
+            raise ValueError("grad_report needs the fused update (FusedClipAdamW.eligible: torch.optim.AdamW / HFAdamW whose parameter groups all hold a "
+                             "device learning rate, over fp32 device parameters): the report runs over its descriptor table")
+        self.report = report
         if monitor is not None and not FusedClipAdamW.eligible(opt, flat.params if isinstance(flat, GradientAverager) else flat):
             raise ValueError("skip_nonfinite needs the fused update (FusedClipAdamW.eligible: torch.optim.AdamW / HFAdamW whose parameter groups all hold a "
                              "device learning rate, over fp32 device parameters): the stock optimizer path cannot skip an update without a host synchronisation")
@@ -1310,7 +1445,7 @@ class FlatGradientTail:
             l.grad = None
         self.fused = None
         if FusedClipAdamW.eligible(opt, self.flat.params):
-            self.fused = FusedClipAdamW(opt, self.flat.params, self.flat_view_of, low_of, clip, monitor=monitor)
+            self.fused = FusedClipAdamW(opt, self.flat.params, self.flat_view_of, low_of, clip, monitor=monitor, report=report)
         # hand-over and clip norm in one pass; with an exchange between the hand-over and the update (N > 1) the hand-over still runs as one pass, its norm is
         # discarded and FusedClipAdamW.update takes the norm of the REDUCED buffers in one more launch
         self.handover = FusedHandOver(len(self.pairs), captures=capture_tables) if (self.fused is not None and FUSED_HANDOVER) else None
@@ -1357,6 +1492,8 @@ class FlatGradientTail:
         self.flat.zero_grad()
         if self.monitor is not None:                         # the warm-up's losses and updates are not the run's
             self.monitor.reset()
+        if self.report is not None:
+            self.report.reset()
 
     # -- the graphed half of a step's state_dict() / load_state_dict() (step_state.py; the eager half: step_state.EagerTail)
     def require_single_rank(self, what):
@@ -1423,7 +1560,7 @@ class GraphedTargetStep(StepState):
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
                  swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None,
-                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None):
+                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None, grad_report: bool = False):
         """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
@@ -1463,6 +1600,7 @@ class GraphedTargetStep(StepState):
         (NotImplementedError, as frame_capacity).  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.  Under an active
         averager ranks may hold different numbers of real rows: pass `global_rows` to the call (ROW_WEIGHT_NOTE).
         `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too; several capacities share the one monitor.
+        `grad_report`: REPORT_NOTE -- `step.grad_report`, a GradReport named by named_step_parameters(multimodal_model, masters).
         `color_jitter` (an augment.ColorJitter; None: no augmentation, the launches of before): the MELD train transform (utils/dataset.py:35-39,
         62-63) inside the uint8 pre-step.  The draw of the per-frame table is PART of every capture in front of Swin's forward (every capacity's, and
         graph S of pipeline_swin): one torch.rand on the device generator and elementwise launches, so every replay jitters anew and a resumed
@@ -1518,13 +1656,14 @@ class GraphedTargetStep(StepState):
         if flat._handles:
             raise ValueError("GraphedTargetStep needs GradientAverager(..., hooks=False): the exchange runs between the graphs")
         self.monitor = TrainMonitor(dev) if skip_nonfinite else None
+        self.grad_report = GradReport(named_step_parameters(self.mm, masters)) if grad_report else None
         # ROW_WEIGHT_NOTE.  Padded rows under an exchange: the all-reduce takes the mean of the ranks' means, which is the mean over the real rows
         # only when every rank holds as many.  One static fp32 word multiplies the loss that is DIFFERENTIATED (row_weight: b * world /
         # global_rows, filled per call; 1.0 without global_rows); the loss returned and the one the monitor counts stay the rank's own mean.
         # Captures without (pad_rows and an active exchange) have no such word and keep their launch sequence.
         self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and flat.active) else None
         self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.trg_accumulation_steps > 1, masters=masters, exchanging=bool(flat.active),
-                                            capture_tables=max(4, len(self.capacities or ())), monitor=self.monitor)
+                                            capture_tables=max(4, len(self.capacities or ())), monitor=self.monitor, report=self.grad_report)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         self.mm.text_stream = None
         # inside ONE graph the fork / join below become parallel branches; which hardware queue the branches replay on is the
@@ -2159,7 +2298,7 @@ class GraphedAuxStep(StepState):
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "aux", ("swin",), "aux_accumulation_steps"
 
     def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False,
-                 skip_nonfinite: bool = False, augment=None):
+                 skip_nonfinite: bool = False, augment=None, grad_report: bool = False):
         """`pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
         pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
         device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
@@ -2167,6 +2306,7 @@ class GraphedAuxStep(StepState):
         Under an active averager `__call__(images, labels, global_rows=...)` weights the differentiated loss with row_weight (ROW_WEIGHT_NOTE at
         GraphedTargetStep): ranks that hold different numbers of real rows then step on the mean over all real rows.
         `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too.
+        `grad_report`: REPORT_NOTE -- `step.grad_report`, a GradReport named by swin_model.named_parameters().
         `augment` (an augment.AffWildAugment; None: no augmentation, the launches of before): the Aff-Wild2 train transform (utils/util.py:22-60)
         inside the uint8 pre-step.  The draw of the per-image table is PART of graph A, in front of Swin's forward: every replay augments anew and a
         resumed generator walks the same tables (nothing is added to state_dict()).  With pad_rows the padded zero images get records too; their
@@ -2189,7 +2329,9 @@ class GraphedAuxStep(StepState):
         flat = averager if averager is not None else GradientAverager(self.swin.parameters(), hooks=False)
         self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and flat.active) else None
         self.monitor = TrainMonitor(dev) if skip_nonfinite else None
-        self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.aux_accumulation_steps > 1, exchanging=bool(flat.active), monitor=self.monitor)
+        self.grad_report = GradReport(self.swin.named_parameters()) if grad_report else None
+        self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.aux_accumulation_steps > 1, exchanging=bool(flat.active), monitor=self.monitor,
+                                            report=self.grad_report)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.swin.parameters()) + list(self.swin.buffers())]
         cap = distinct_stream(dev)
@@ -2332,13 +2474,14 @@ class GraphedUnimodalStep(StepState):
     -100) and replayed through the same graphs, flat buffers and optimizer state; the loss returned is the mean over the b real rows /
     trg_accumulation_steps.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
     `skip_nonfinite`: GUARD_NOTE -- the learning-rate schedule advances on a skipped update too.
+    `grad_report`: REPORT_NOTE -- `step.grad_report`, a GradReport named by model.named_parameters().
     `averager` (default None: this step never exchanges): a GradientAverager(hooks=False) over the model's parameters -- its buckets are averaged
     over the ranks between graph A and graph B of a window's last micro-step, as GraphedAuxStep does it; with pad_rows the call then takes
     `global_rows` (ROW_WEIGHT_NOTE at GraphedTargetStep)."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = UnimodalStep.STATE_KIND, UnimodalStep.STATE_MODELS, UnimodalStep.STATE_WINDOW
 
     def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False,
-                 skip_nonfinite: bool = False, averager=None):
+                 skip_nonfinite: bool = False, averager=None, grad_report: bool = False):
         from . import ops
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
         self.autocast_dtype = autocast_dtype
@@ -2354,8 +2497,10 @@ class GraphedUnimodalStep(StepState):
         self.exchange = averager.exchange_all if averager is not None else None
         self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and averager is not None and averager.active) else None
         self.monitor = TrainMonitor(dev) if skip_nonfinite else None
+        self.grad_report = GradReport(self.model.named_parameters()) if grad_report else None
         self.tail = tail = FlatGradientTail(averager if averager is not None else self.model.parameters(), optimizer, args.clip,
-                                            args.trg_accumulation_steps > 1, exchanging=bool(averager is not None and averager.active), monitor=self.monitor)
+                                            args.trg_accumulation_steps > 1, exchanging=bool(averager is not None and averager.active), monitor=self.monitor,
+                                            report=self.grad_report)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         snap = [(t, t.detach().clone()) for t in list(self.model.parameters()) + list(self.model.buffers())]
         cap = distinct_stream(dev)

@@ -533,6 +533,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_aug.h"
 /* Clip + AdamW over parameter groups, learning rate / betas / eps / weight decay per record (fmmt_adamw_groups, fmmt_adamw_groups_guarded): likewise, held to _lib.GROUPS_SIGNATURES. */
 #include "fmmt_groups.h"
+/* Per-tensor statistics over the optimizer's descriptor table, and the snapshot of a bad update (fmmt_table_stats): likewise, held to _lib.STATS_SIGNATURES. */
+#include "fmmt_stats.h"
 
 #ifdef __cplusplus
 }
