@@ -182,6 +182,18 @@ STATS_G, STATS_P, STATS_M, STATS_V = 0, 1, 2, 3
 STATS_BYTES, STATS_BAD_WORDS = 16, 2
 STATS_FIELDS = [("sumsq", "<f4"), ("max_abs", "<f4"), ("nonfinite", "<i4"), ("reserved", "<i4")]
 
+# include/fmmt_tokens.h, one to one: a thirteenth table and header -- the text encoder on real tokens only: the token layout of a padding mask, the
+# unpack of packed rows, the attention core's ragged mode, the sublayer tails with a row map (tests/test_tokens_cpu.py holds table, header and library together)
+TOKENS_SIGNATURES = {
+    "fmmt_token_layout": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "fmmt_unpack_rows": (_i, [_i, _i, _i, _sz, _p, _p, _p, _p]),
+    "fmmt_mha_fwd_ragged": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _f, _f, _u64, _p, _p, _i, _p, _p]),
+    "fmmt_mha_bwd_ragged": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _f, _f, _u64, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i, _p]),
+    "fmmt_dropadd_ln_fwd_map": (_i, [_i, _i, _i, _f, _p, _p, _p, _p, _f, _u64, _p, _u64, _p, _p, _p, _p]),
+    "fmmt_dropadd_ln_bwd_map": (_i, [_i, _i, _i, _f, _p, _p, _p, _f, _u64, _p, _u64, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+}
+RAGGED = 0x800          # include/fmmt_tokens.h FMMT_RAGGED: the dtype flag fmmt_mha_fwd_ragged / _bwd_ragged ask for
+
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
 _ERR = {-1: "FMMT_EINVAL (bad shape / unsupported size)", -2: "FMMT_EALIGN (pointer or leading dimension not 16-byte aligned)",
         -3: "FMMT_EWORKSPACE (workspace too small)"}
@@ -202,7 +214,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + list(TOKENS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -813,3 +813,41 @@ extern "C" int fmmt_mha_bwd(int dtype, int Lq, int Lk, int B, int E, int num_hea
     FMMT_MHA_DISPATCH(K_DK, (Lk + 63) / 64);
     return 0;
 }
+
+// Self-attention on packed rows (include/fmmt_tokens.h): the matrix-core kernels' ragged mode only -- there is no second formulation to fall to
+namespace {
+int mha_ragged_args(MhaArgs& a, int dtype, int T, int B, int E, int num_heads, int rows, const int32_t* seq_off, const int32_t* seq_len, int ldq, int ldkv,
+                    int ldo, float dropout_p) {
+    if (dtype != (FMMT_BF16 | FMMT_RAGGED)) return FMMT_EINVAL;
+    if (int e = mha_check(FMMT_BF16, T, T, B, E, num_heads)) return e;
+    if (E / num_heads != 64 || rows <= 0 || (long long)rows > (long long)B * T || !seq_off || !seq_len) return FMMT_EINVAL;
+    if (dropout_p < 0.f || dropout_p >= 1.f) return FMMT_EINVAL;
+    if (ldq % 8 || ldkv % 8 || ldo % 8) return FMMT_EALIGN;
+    a.Lq = T; a.Lk = T; a.B = B; a.E = E; a.nH = num_heads; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.drop_p = dropout_p;
+    a.bm = 2; a.seq_off = seq_off; a.seq_len = seq_len; a.rows = rows;
+    return 0;
+}
+}  // namespace
+
+extern "C" int fmmt_mha_fwd_ragged(int dtype, int T, int B, int E, int num_heads, int rows, const int32_t* seq_off, const int32_t* seq_len,
+                                   const void* q, int ldq, const void* k, const void* v, int ldkv, float scale,
+                                   float dropout_p, uint64_t seed, const uint64_t* seed_dev, void* out, int ldo, float* lse, void* stream) {
+    MhaArgs a{};
+    if (int e = mha_ragged_args(a, dtype, T, B, E, num_heads, rows, seq_off, seq_len, ldq, ldkv, ldo, dropout_p)) return e;
+    if (!q || !k || !v || !out || !lse) return FMMT_EINVAL;
+    a.q = q; a.k = k; a.v = v; a.scale = scale; a.seed = seed; a.seed_dev = seed_dev; a.out = out; a.lse = lse;
+    return fmmt_mha_mfma_fwd_launch(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int fmmt_mha_bwd_ragged(int dtype, int T, int B, int E, int num_heads, int rows, const int32_t* seq_off, const int32_t* seq_len,
+                                   const void* q, int ldq, const void* k, const void* v, int ldkv, float scale,
+                                   float dropout_p, uint64_t seed, const uint64_t* seed_dev, const void* out, const void* dout, int ldo,
+                                   const float* lse, void* dq, int lddq, void* dk, void* dv, int lddkv, void* stream) {
+    MhaArgs a{};
+    if (int e = mha_ragged_args(a, dtype, T, B, E, num_heads, rows, seq_off, seq_len, ldq, ldkv, ldo, dropout_p)) return e;
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv) return FMMT_EINVAL;
+    if (lddq % 8 || lddkv % 8) return FMMT_EALIGN;
+    a.q = q; a.k = k; a.v = v; a.scale = scale; a.seed = seed; a.seed_dev = seed_dev; a.out = const_cast<void*>(out); a.lse = const_cast<float*>(lse);
+    a.dout = dout; a.dq = dq; a.lddq = lddq; a.dk = dk; a.dv = dv; a.lddkv = lddkv;
+    return fmmt_mha_mfma_bwd_launch(a, reinterpret_cast<hipStream_t>(stream));
+}

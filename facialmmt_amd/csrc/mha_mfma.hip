@@ -80,6 +80,43 @@ __device__ __forceinline__ void block_of(int& bx, int& bh) {
     bx = w - bh * nx;
 }
 
+// One (batch) sequence as a kernel sees it.  Dense modes: Lq x Lk of the launch, rows by MhaArgs::rq / rk.  Ragged mode (bm == 2, self-attention on
+// packed rows): len[b] queries = keys at rows off[b] + t; p.Lq == p.Lk == T stays the PADDED length -- the grid, lse's pitch and the dropout counters
+// are those of the padded batch-major call, so a ragged launch computes bit for bit what that call computes on the real rows (a key past the end takes
+// the "past the last key" term; the padded call's -30000 bias underflows to the same zero probability).  The length is clamped to what the packed
+// operands hold: no index leaves [0, p.rows) whatever the two arrays say.
+struct Seq {
+    int Lq, Lk, base;               // base < 0: dense
+    __device__ __forceinline__ size_t rq(const MhaArgs& p, int t, int b) const { return base >= 0 ? (size_t)(base + t) : p.rq(t, b); }
+    __device__ __forceinline__ size_t rk(const MhaArgs& p, int t, int b) const { return base >= 0 ? (size_t)(base + t) : p.rk(t, b); }
+};
+__device__ __forceinline__ int ragged_len(const MhaArgs& p, int b) {
+    const int off = p.seq_off[b];
+    if (off < 0 || off >= p.rows) return 0;
+    return max(0, min(min(p.seq_len[b], p.Lq), p.rows - off));
+}
+__device__ __forceinline__ Seq seq_of(const MhaArgs& p, int b) {
+    if (p.bm != 2) return Seq{p.Lq, p.Lk, -1};
+    const int n = ragged_len(p, b);
+    return Seq{n, n, n > 0 ? p.seq_off[b] : 0};
+}
+// Ragged mode: the rows behind the last sequence, [total, p.rows), are nobody's queries or keys, yet the GEMMs around the attention contract over
+// them: they are zero-filled by the dead slots (b, t), len[b] <= t < T, of the static grid -- B * T - total of them, numbered in (b, t) order, which
+// covers the filler because p.rows <= B * T.  Returns the row slot (b, t) zeroes, or -1.
+__device__ __forceinline__ int filler_row(const MhaArgs& p, const Seq& s, int b, int t) {
+    if (s.base < 0 || t < s.Lq || t >= p.Lq) return -1;
+    const int total = p.seq_off[p.B - 1] + ragged_len(p, p.B - 1);
+    const long long r = (long long)total + ((long long)b * p.Lq - p.seq_off[b]) + (t - s.Lq);
+    return (total >= 0 && r >= total && r < p.rows) ? (int)r : -1;
+}
+__device__ __forceinline__ void zero_row(bf16* dst, int lg) {
+    bf16x8 z;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = (bf16)0.f;
+    *reinterpret_cast<bf16x8*>(dst + lg * 8) = z;
+    *reinterpret_cast<bf16x8*>(dst + 32 + lg * 8) = z;
+}
+
 // a wave's 16 rows of a 64-row tile: row r0 + wave*16 + li, 16-byte pieces lg*8 and 32 + lg*8; rows >= L read as zero
 struct RowRegs { bf16x8 v[2]; };
 __device__ __forceinline__ RowRegs fetch_row(const bf16* base, size_t rowoff, bool ok) {
@@ -154,8 +191,8 @@ __device__ __forceinline__ void fwd_tile(const AttnDrop& dr, const bf16* Kt, con
 }
 
 // the per-key term of key `key` (log2 domain); the first 64 threads of a workgroup fetch one each with the tile
-__device__ __forceinline__ float key_term(const MhaArgs& p, int b, int key) {
-    return key < p.Lk ? (p.key_bias ? p.key_bias[(size_t)b * p.Lk + key] * LOG2E : 0.f) : NEG_BIG;
+__device__ __forceinline__ float key_term(const MhaArgs& p, int Lk, int b, int key) {
+    return key < Lk ? (p.key_bias ? p.key_bias[(size_t)b * p.Lk + key] * LOG2E : 0.f) : NEG_BIG;
 }
 
 template <bool DROP>
@@ -168,13 +205,19 @@ __global__ __launch_bounds__(256) void mha_mfma_fwd_kernel(MhaArgs p) {
     block_of(bx, bh);
     const int b = bh / p.nH, h = bh - b * p.nH;
     const int q0 = bx * 64 + wave * 16, sr = wave * 16 + li;
-    const bool active = q0 < p.Lq;                          // wave-uniform: a wave whose 16 queries are all past the end only helps staging
+    const Seq sq = seq_of(p, b);
+    if (bx * 64 >= sq.Lq) {                                 // ragged mode only (the grid is sized by the padded length): nothing to compute, uniform
+        const int fr = filler_row(p, sq, b, q0 + li);
+        if (fr >= 0) zero_row(reinterpret_cast<bf16*>(p.out) + (size_t)fr * p.ldo + h * D, lg);
+        return;
+    }
+    const bool active = q0 < sq.Lq;                         // wave-uniform: a wave whose 16 queries are all past the end only helps staging
     const bf16* kg = reinterpret_cast<const bf16*>(p.k) + h * D + lg * 8;
     const bf16* vg = reinterpret_cast<const bf16*>(p.v) + h * D + lg * 8;
-    const int q = min(q0 + li, p.Lq - 1);
+    const int q = min(q0 + li, sq.Lq - 1);
     bf16x8 qf[2];
     {
-        const bf16* src = reinterpret_cast<const bf16*>(p.q) + p.rq(q, b) * p.ldq + h * D + lg * 8;
+        const bf16* src = reinterpret_cast<const bf16*>(p.q) + sq.rq(p, q, b) * p.ldq + h * D + lg * 8;
         qf[0] = ldg8(src);
         qf[1] = ldg8(src + 32);
     }
@@ -186,27 +229,29 @@ __global__ __launch_bounds__(256) void mha_mfma_fwd_kernel(MhaArgs p) {
     float m = NEG_BIG, l = 0.f;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    RowRegs kr = fetch_row(kg, p.rk(min(sr, p.Lk - 1), b) * p.ldkv, sr < p.Lk);
-    RowRegs vr = fetch_row(vg, p.rk(min(sr, p.Lk - 1), b) * p.ldkv, sr < p.Lk);
-    float kbr = wave == 0 ? key_term(p, b, lane) : 0.f;
-    for (int j0 = 0; j0 < p.Lk; j0 += 64) {
+    RowRegs kr = fetch_row(kg, sq.rk(p, min(sr, sq.Lk - 1), b) * p.ldkv, sr < sq.Lk);
+    RowRegs vr = fetch_row(vg, sq.rk(p, min(sr, sq.Lk - 1), b) * p.ldkv, sr < sq.Lk);
+    float kbr = wave == 0 ? key_term(p, sq.Lk, b, lane) : 0.f;
+    for (int j0 = 0; j0 < sq.Lk; j0 += 64) {
         __syncthreads();
         put_row(Kt, sr, lg, kr);
         put_row(Vt, sr, lg, vr);
         if (wave == 0) Kb[lane] = kbr;
         __syncthreads();
-        if (j0 + 64 < p.Lk) {
+        if (j0 + 64 < sq.Lk) {
             const int row = j0 + 64 + sr;
-            const size_t off = p.rk(min(row, p.Lk - 1), b) * p.ldkv;
-            kr = fetch_row(kg, off, row < p.Lk);
-            vr = fetch_row(vg, off, row < p.Lk);
-            if (wave == 0) kbr = key_term(p, b, j0 + 64 + lane);
+            const size_t off = sq.rk(p, min(row, sq.Lk - 1), b) * p.ldkv;
+            kr = fetch_row(kg, off, row < sq.Lk);
+            vr = fetch_row(vg, off, row < sq.Lk);
+            if (wave == 0) kbr = key_term(p, sq.Lk, b, j0 + 64 + lane);
         }
         if (active) fwd_tile<DROP>(dr, Kt, Vt, Kb, qf, o, m, l, c2, drow, j0, li, lg);
     }
-    if (q0 + li < p.Lq) {
-        store_row(reinterpret_cast<bf16*>(p.out) + p.rq(q, b) * p.ldo + h * D, o, 1.0f / l, lg);
+    if (q0 + li < sq.Lq) {
+        store_row(reinterpret_cast<bf16*>(p.out) + sq.rq(p, q, b) * p.ldo + h * D, o, 1.0f / l, lg);
         if (lg == 0) p.lse[(size_t)bh * p.Lq + q] = (m + __log2f(l)) * LN2;
+    } else if (const int fr = filler_row(p, sq, b, q0 + li); fr >= 0) {
+        zero_row(reinterpret_cast<bf16*>(p.out) + (size_t)fr * p.ldo + h * D, lg);
     }
 }
 
@@ -252,17 +297,23 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dq_kernel(MhaArgs p) {
     block_of(bx, bh);
     const int b = bh / p.nH, h = bh - b * p.nH;
     const int q0 = bx * 64 + wave * 16, sr = wave * 16 + li;
-    const bool active = q0 < p.Lq;
+    const Seq sq = seq_of(p, b);
+    if (bx * 64 >= sq.Lq) {                                 // ragged mode only: uniform
+        const int fr = filler_row(p, sq, b, q0 + li);
+        if (fr >= 0) zero_row(reinterpret_cast<bf16*>(p.dq) + (size_t)fr * p.lddq + h * D, lg);
+        return;
+    }
+    const bool active = q0 < sq.Lq;
     const bf16* kg = reinterpret_cast<const bf16*>(p.k) + h * D + lg * 8;
     const bf16* vg = reinterpret_cast<const bf16*>(p.v) + h * D + lg * 8;
-    const int q = min(q0 + li, p.Lq - 1);
+    const int q = min(q0 + li, sq.Lq - 1);
     bf16x8 qf[2], gf[2];
     float dl;
     {
-        const bf16* src = reinterpret_cast<const bf16*>(p.q) + p.rq(q, b) * p.ldq + h * D + lg * 8;
+        const bf16* src = reinterpret_cast<const bf16*>(p.q) + sq.rq(p, q, b) * p.ldq + h * D + lg * 8;
         qf[0] = ldg8(src);
         qf[1] = ldg8(src + 32);
-        const size_t orow = p.rq(q, b) * p.ldo + h * D + lg * 8;
+        const size_t orow = sq.rq(p, q, b) * p.ldo + h * D + lg * 8;
         gf[0] = ldg8(reinterpret_cast<const bf16*>(p.dout) + orow);
         gf[1] = ldg8(reinterpret_cast<const bf16*>(p.dout) + orow + 32);
         const bf16x8 o0 = ldg8(reinterpret_cast<const bf16*>(p.out) + orow), o1 = ldg8(reinterpret_cast<const bf16*>(p.out) + orow + 32);
@@ -279,25 +330,26 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dq_kernel(MhaArgs p) {
     f32x4 dq[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    RowRegs kr = fetch_row(kg, p.rk(min(sr, p.Lk - 1), b) * p.ldkv, sr < p.Lk);
-    RowRegs vr = fetch_row(vg, p.rk(min(sr, p.Lk - 1), b) * p.ldkv, sr < p.Lk);
-    float kbr = wave == 0 ? key_term(p, b, lane) : 0.f;
-    for (int j0 = 0; j0 < p.Lk; j0 += 64) {
+    RowRegs kr = fetch_row(kg, sq.rk(p, min(sr, sq.Lk - 1), b) * p.ldkv, sr < sq.Lk);
+    RowRegs vr = fetch_row(vg, sq.rk(p, min(sr, sq.Lk - 1), b) * p.ldkv, sr < sq.Lk);
+    float kbr = wave == 0 ? key_term(p, sq.Lk, b, lane) : 0.f;
+    for (int j0 = 0; j0 < sq.Lk; j0 += 64) {
         __syncthreads();
         put_row(Kt, sr, lg, kr);
         put_row(Vt, sr, lg, vr);
         if (wave == 0) Kb[lane] = kbr;
         __syncthreads();
-        if (j0 + 64 < p.Lk) {
+        if (j0 + 64 < sq.Lk) {
             const int row = j0 + 64 + sr;
-            const size_t off = p.rk(min(row, p.Lk - 1), b) * p.ldkv;
-            kr = fetch_row(kg, off, row < p.Lk);
-            vr = fetch_row(vg, off, row < p.Lk);
-            if (wave == 0) kbr = key_term(p, b, j0 + 64 + lane);
+            const size_t off = sq.rk(p, min(row, sq.Lk - 1), b) * p.ldkv;
+            kr = fetch_row(kg, off, row < sq.Lk);
+            vr = fetch_row(vg, off, row < sq.Lk);
+            if (wave == 0) kbr = key_term(p, sq.Lk, b, j0 + 64 + lane);
         }
         if (active) dq_tile<DROP>(dr, Kt, Vt, Kb, qf, gf, dq, ls2, dl, c2, drow, j0, li, lg);
     }
-    if (q0 + li < p.Lq) store_row(reinterpret_cast<bf16*>(p.dq) + p.rq(q, b) * p.lddq + h * D, dq, p.scale, lg);
+    if (q0 + li < sq.Lq) store_row(reinterpret_cast<bf16*>(p.dq) + sq.rq(p, q, b) * p.lddq + h * D, dq, p.scale, lg);
+    else if (const int fr = filler_row(p, sq, b, q0 + li); fr >= 0) zero_row(reinterpret_cast<bf16*>(p.dq) + (size_t)fr * p.lddq + h * D, lg);
 }
 
 // =============================================================================================
@@ -313,14 +365,23 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dkv_kernel(MhaArgs p) {
     block_of(bx, bh);
     const int b = bh / p.nH, h = bh - b * p.nH;
     const int k0 = bx * 64 + wave * 16, sr = wave * 16 + li;
-    const bool active = k0 < p.Lk;
+    const Seq sq = seq_of(p, b);
+    if (bx * 64 >= sq.Lk) {                                 // ragged mode only: uniform
+        const int fr = filler_row(p, sq, b, k0 + li);
+        if (fr >= 0) {
+            zero_row(reinterpret_cast<bf16*>(p.dk) + (size_t)fr * p.lddkv + h * D, lg);
+            zero_row(reinterpret_cast<bf16*>(p.dv) + (size_t)fr * p.lddkv + h * D, lg);
+        }
+        return;
+    }
+    const bool active = k0 < sq.Lk;
     const bf16* qg = reinterpret_cast<const bf16*>(p.q) + h * D + lg * 8;
     const bf16* og = reinterpret_cast<const bf16*>(p.out) + h * D + lg * 8;
     const bf16* gg = reinterpret_cast<const bf16*>(p.dout) + h * D + lg * 8;
-    const int key = min(k0 + li, p.Lk - 1);
+    const int key = min(k0 + li, sq.Lk - 1);
     bf16x8 kf[2], vf[2];
     {
-        const size_t off = p.rk(key, b) * p.ldkv + h * D + lg * 8;
+        const size_t off = sq.rk(p, key, b) * p.ldkv + h * D + lg * 8;
         kf[0] = ldg8(reinterpret_cast<const bf16*>(p.k) + off);
         kf[1] = ldg8(reinterpret_cast<const bf16*>(p.k) + off + 32);
         vf[0] = ldg8(reinterpret_cast<const bf16*>(p.v) + off);
@@ -342,10 +403,10 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dkv_kernel(MhaArgs p) {
     float dpre, lpre;
     auto fetch = [&](int i0) {
         const int row = i0 + sr;
-        const bool ok = row < p.Lq;
-        const int rc = min(row, p.Lq - 1);
-        qr = fetch_row(qg, p.rq(rc, b) * p.ldq, ok);
-        const size_t off = p.rq(rc, b) * p.ldo;
+        const bool ok = row < sq.Lq;
+        const int rc = min(row, sq.Lq - 1);
+        qr = fetch_row(qg, sq.rq(p, rc, b) * p.ldq, ok);
+        const size_t off = sq.rq(p, rc, b) * p.ldo;
         gr = fetch_row(gg, off, ok);
         const bf16x8 o0 = ldg8(og + off), o1 = ldg8(og + off + 32);
         float d = 0.f;
@@ -355,7 +416,7 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dkv_kernel(MhaArgs p) {
         lpre = ok ? p.lse[(size_t)bh * p.Lq + rc] * LOG2E : -NEG_BIG;
     };
     fetch(0);
-    for (int i0 = 0; i0 < p.Lq; i0 += 64) {
+    for (int i0 = 0; i0 < sq.Lq; i0 += 64) {
         __syncthreads();
         put_row(Qt, sr, lg, qr);
         put_row(Gt, sr, lg, gr);
@@ -364,7 +425,7 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dkv_kernel(MhaArgs p) {
             Ls[sr] = lpre;
         }
         __syncthreads();
-        if (i0 + 64 < p.Lq) fetch(i0 + 64);
+        if (i0 + 64 < sq.Lq) fetch(i0 + 64);
         if (!active) continue;
         float pp[16], ds[16];
 #pragma unroll
@@ -415,10 +476,13 @@ __global__ __launch_bounds__(256) void mha_mfma_bwd_dkv_kernel(MhaArgs p) {
             dk[dt] = mfma(tr_fragT(Qt, 32 + 4 * lg, dt, li), d1, dk[dt]);
         }
     }
-    if (k0 + li < p.Lk) {
-        const size_t off = p.rk(key, b) * p.lddkv + h * D;
+    if (k0 + li < sq.Lk) {
+        const size_t off = sq.rk(p, key, b) * p.lddkv + h * D;
         store_row(reinterpret_cast<bf16*>(p.dk) + off, dk, p.scale, lg);
         store_row(reinterpret_cast<bf16*>(p.dv) + off, dv, 1.0f, lg);
+    } else if (const int fr = filler_row(p, sq, b, k0 + li); fr >= 0) {
+        zero_row(reinterpret_cast<bf16*>(p.dk) + (size_t)fr * p.lddkv + h * D, lg);
+        zero_row(reinterpret_cast<bf16*>(p.dv) + (size_t)fr * p.lddkv + h * D, lg);
     }
 }
 

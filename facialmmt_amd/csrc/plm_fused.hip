@@ -40,7 +40,7 @@ template <typename P>
 __global__ __launch_bounds__(256) void plm_dropadd_ln_fwd_kernel(int M, int C, float eps, const bf16* __restrict__ h, const bf16* __restrict__ res,
                                                                  const P* __restrict__ gamma, const P* __restrict__ beta, float p,
                                                                  unsigned long long seed_i, const unsigned long long* __restrict__ seed_ptr, unsigned long long salt,
-                                                                 bf16* __restrict__ xsum, bf16* __restrict__ y) {
+                                                                 bf16* __restrict__ xsum, bf16* __restrict__ y, const int* __restrict__ row_map) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = C / 8;
     const float invC = 1.0f / (float)C;
@@ -49,6 +49,7 @@ __global__ __launch_bounds__(256) void plm_dropadd_ln_fwd_kernel(int M, int C, f
     for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
         bf16x8 xv[PF_MAXV];
         float s = 0.f;
+        const size_t crow = (size_t)(row_map ? row_map[row] : row) * C;      // the generator's counter: the row of the layout whose mask is drawn
 #pragma unroll
         for (int i = 0; i < PF_MAXV; ++i) {
             const int v = lane + 64 * i;
@@ -56,7 +57,8 @@ __global__ __launch_bounds__(256) void plm_dropadd_ln_fwd_kernel(int M, int C, f
                 const size_t o = (size_t)row * C + v * 8;
                 const bf16x8 hv = *reinterpret_cast<const bf16x8*>(h + o), rv = *reinterpret_cast<const bf16x8*>(res + o);
                 uint32_t keep = 0xFFu;
-                if (p > 0.f) keep = elem_keep4(dr, (uint32_t)(o >> 2)) | (elem_keep4(dr, (uint32_t)(o >> 2) + 1u) << 4);
+                const size_t oc = crow + v * 8;
+                if (p > 0.f) keep = elem_keep4(dr, (uint32_t)(oc >> 2)) | (elem_keep4(dr, (uint32_t)(oc >> 2) + 1u) << 4);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     float t = (float)hv[e];
@@ -97,7 +99,7 @@ template <typename P>
 __global__ __launch_bounds__(512) void plm_dropadd_ln_bwd_kernel(int M, int C, float eps, const bf16* __restrict__ dy, const bf16* __restrict__ x,
                                                                  const P* __restrict__ gamma, float p, unsigned long long seed_i,
                                                                  const unsigned long long* __restrict__ seed_ptr, unsigned long long salt, bf16* __restrict__ dx, bf16* __restrict__ dh,
-                                                                 float* __restrict__ part) {
+                                                                 float* __restrict__ part, const int* __restrict__ row_map) {
     __shared__ float red[PF_BW][3][64 * 8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nv = C / 8;
@@ -112,6 +114,7 @@ __global__ __launch_bounds__(512) void plm_dropadd_ln_bwd_kernel(int M, int C, f
     for (int row = blockIdx.x * PF_BW + wave; row < M; row += gridDim.x * PF_BW) {
         bf16x8 xv[PF_MAXV], gv[PF_MAXV];
         float s = 0.f;
+        const size_t crow = (size_t)(row_map ? row_map[row] : row) * C;
 #pragma unroll
         for (int i = 0; i < PF_MAXV; ++i) {
             const int v = lane + 64 * i;
@@ -159,7 +162,8 @@ __global__ __launch_bounds__(512) void plm_dropadd_ln_bwd_kernel(int M, int C, f
                 pf_load8<P>(gamma + v * 8, gm);
                 bf16x8 ox, oh;
                 uint32_t keep = 0xFFu;
-                if (p > 0.f) keep = elem_keep4(dr, (uint32_t)(o >> 2)) | (elem_keep4(dr, (uint32_t)(o >> 2) + 1u) << 4);
+                const size_t oc = crow + v * 8;
+                if (p > 0.f) keep = elem_keep4(dr, (uint32_t)(oc >> 2)) | (elem_keep4(dr, (uint32_t)(oc >> 2) + 1u) << 4);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float xh = ((float)xv[i][e] - mean) * rstd, g = (float)gv[i][e] * gm[e];
@@ -433,8 +437,8 @@ bool pf_misaligned(const void* a, const void* b, const void* c, const void* d) {
 
 }  // namespace
 
-extern "C" int fmmt_dropadd_ln_fwd(int param_dtype, int M, int C, float eps, const void* h, const void* res, const void* gamma, const void* beta, float p,
-                                   uint64_t seed, const uint64_t* seed_dev, uint64_t salt, void* xsum, void* y, void* stream) {
+extern "C" int fmmt_dropadd_ln_fwd_map(int param_dtype, int M, int C, float eps, const void* h, const void* res, const void* gamma, const void* beta, float p,
+                                       uint64_t seed, const uint64_t* seed_dev, uint64_t salt, void* xsum, void* y, const int32_t* row_map, void* stream) {
     if (M <= 0 || C <= 0 || C % 8 || C > 2048 || !(p >= 0.f && p < 1.f)) return FMMT_EINVAL;
     if (param_dtype != FMMT_BF16 && param_dtype != FMMT_F32) return FMMT_EINVAL;
     if (!h || !res || !gamma || !beta || !xsum || !y) return FMMT_EINVAL;
@@ -442,12 +446,17 @@ extern "C" int fmmt_dropadd_ln_fwd(int param_dtype, int M, int C, float eps, con
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (param_dtype == FMMT_BF16)
         hipLaunchKernelGGL(plm_dropadd_ln_fwd_kernel<bf16>, dim3(pf_blocks_fwd(M)), dim3(256), 0, st, M, C, eps, (const bf16*)h, (const bf16*)res, (const bf16*)gamma,
-                           (const bf16*)beta, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)xsum, (bf16*)y);
+                           (const bf16*)beta, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)xsum, (bf16*)y, (const int*)row_map);
     else
         hipLaunchKernelGGL(plm_dropadd_ln_fwd_kernel<float>, dim3(pf_blocks_fwd(M)), dim3(256), 0, st, M, C, eps, (const bf16*)h, (const bf16*)res, (const float*)gamma,
-                           (const float*)beta, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)xsum, (bf16*)y);
+                           (const float*)beta, p, (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)xsum, (bf16*)y, (const int*)row_map);
     FMMT_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int fmmt_dropadd_ln_fwd(int param_dtype, int M, int C, float eps, const void* h, const void* res, const void* gamma, const void* beta, float p,
+                                   uint64_t seed, const uint64_t* seed_dev, uint64_t salt, void* xsum, void* y, void* stream) {
+    return fmmt_dropadd_ln_fwd_map(param_dtype, M, C, eps, h, res, gamma, beta, p, seed, seed_dev, salt, xsum, y, nullptr, stream);
 }
 
 extern "C" size_t fmmt_dropadd_ln_bwd_workspace(int M, int C) {
@@ -455,9 +464,9 @@ extern "C" size_t fmmt_dropadd_ln_bwd_workspace(int M, int C) {
     return (size_t)pf_blocks(M) * 3 * (size_t)C * sizeof(float);
 }
 
-extern "C" int fmmt_dropadd_ln_bwd(int param_dtype, int M, int C, float eps, const void* dy, const void* xsum, const void* gamma, float p, uint64_t seed,
-                                   const uint64_t* seed_dev, uint64_t salt, void* dx, void* dh, void* dgamma, void* dbeta, void* dbias, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
+extern "C" int fmmt_dropadd_ln_bwd_map(int param_dtype, int M, int C, float eps, const void* dy, const void* xsum, const void* gamma, float p, uint64_t seed,
+                                       const uint64_t* seed_dev, uint64_t salt, void* dx, void* dh, void* dgamma, void* dbeta, void* dbias, void* workspace,
+                                       size_t workspace_bytes, const int32_t* row_map, void* stream) {
     if (M <= 0 || C <= 0 || C % 8 || C > 2048 || !(p >= 0.f && p < 1.f)) return FMMT_EINVAL;
     if (param_dtype != FMMT_BF16 && param_dtype != FMMT_F32) return FMMT_EINVAL;
     if (!dy || !xsum || !gamma || !dx || !dh || !dgamma || !dbeta || !workspace) return FMMT_EINVAL;
@@ -468,19 +477,26 @@ extern "C" int fmmt_dropadd_ln_bwd(int param_dtype, int M, int C, float eps, con
     float* part = reinterpret_cast<float*>(workspace);
     if (param_dtype == FMMT_BF16) {
         hipLaunchKernelGGL(plm_dropadd_ln_bwd_kernel<bf16>, dim3(blocks), dim3(64 * PF_BW), 0, st, M, C, eps, (const bf16*)dy, (const bf16*)xsum, (const bf16*)gamma, p,
-                           (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)dx, (bf16*)dh, part);
+                           (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)dx, (bf16*)dh, part, (const int*)row_map);
         FMMT_CHECK_LAUNCH();
         hipLaunchKernelGGL(plm_dropadd_ln_reduce_kernel<bf16>, dim3((3 * C + 31) / 32), dim3(1024), 0, st, (const float*)part, blocks, C, (bf16*)dgamma, (bf16*)dbeta,
                            (bf16*)dbias);
     } else {
         hipLaunchKernelGGL(plm_dropadd_ln_bwd_kernel<float>, dim3(blocks), dim3(64 * PF_BW), 0, st, M, C, eps, (const bf16*)dy, (const bf16*)xsum, (const float*)gamma, p,
-                           (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)dx, (bf16*)dh, part);
+                           (unsigned long long)seed, (const unsigned long long*)seed_dev, (unsigned long long)salt, (bf16*)dx, (bf16*)dh, part, (const int*)row_map);
         FMMT_CHECK_LAUNCH();
         hipLaunchKernelGGL(plm_dropadd_ln_reduce_kernel<float>, dim3((3 * C + 31) / 32), dim3(1024), 0, st, (const float*)part, blocks, C, (float*)dgamma,
                            (float*)dbeta, (float*)dbias);
     }
     FMMT_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int fmmt_dropadd_ln_bwd(int param_dtype, int M, int C, float eps, const void* dy, const void* xsum, const void* gamma, float p, uint64_t seed,
+                                   const uint64_t* seed_dev, uint64_t salt, void* dx, void* dh, void* dgamma, void* dbeta, void* dbias, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    return fmmt_dropadd_ln_bwd_map(param_dtype, M, C, eps, dy, xsum, gamma, p, seed, seed_dev, salt, dx, dh, dgamma, dbeta, dbias, workspace, workspace_bytes,
+                                   nullptr, stream);
 }
 
 // the text encoder's form: bf16 affine parameters

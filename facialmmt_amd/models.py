@@ -178,16 +178,32 @@ class MultiModalTransformerForClassification(nn.Module):
     def text_branch(self, batch_text_input_ids, batch_text_input_mask, batch_text_sep_mask, batchUtt_in_dia_idx):
         """PLM -> text_linear -> tokens of the target utterance (ref :95-150): (B, L_t, H), mask (B, L_t)"""
         plm = self.roberta if self.text_pretrained_model == 'roberta' else self.bert
+        # `text_token_capacity` (set by the training steps, train_step PACK_NOTE; absent or 0: the padded layout): the fused encoder's layers and
+        # text_linear run on the real tokens packed into that many rows; the rows go back to (B, T, H) in front of the slicing, zeros at the padding
+        box = getattr(plm, "_fmmt_box", None)
+        if box is not None:
+            box.capacity = int(getattr(self, "text_token_capacity", 0) or 0)
+        try:
+            text_out = self._plm_forward(plm, batch_text_input_ids, batch_text_input_mask)
+        finally:
+            lay = box.take_layout() if box is not None else None
+            if box is not None:
+                box.capacity = 0
+        text_utt_linear = self.text_linear(text_out.to(self.text_linear.weight.dtype))
+        if lay is not None:
+            from . import ops
+            text_utt_linear = ops.unpack_rows(text_utt_linear[0], lay)
+        return slice_target_utterance(text_utt_linear, batch_text_sep_mask, batchUtt_in_dia_idx,
+                                      self.get_text_utt_max_lens, self.text_pretrained_model == 'roberta')
+
+    @staticmethod
+    def _plm_forward(plm, batch_text_input_ids, batch_text_input_mask):
         if next(plm.parameters()).dtype in (torch.bfloat16, torch.float16) and batch_text_input_ids.is_cuda:
             # a text encoder whose parameters already are low precision (train_step.MasterWeights) runs as it is: autocast
             # would still force its LayerNorms / softmax through fp32 tensors and casts
             with torch.autocast("cuda", enabled=False):
-                text_out = plm(batch_text_input_ids, batch_text_input_mask)[0]
-        else:
-            text_out = plm(batch_text_input_ids, batch_text_input_mask)[0]               # (B, T, plm_hidden)
-        text_utt_linear = self.text_linear(text_out.to(self.text_linear.weight.dtype))
-        return slice_target_utterance(text_utt_linear, batch_text_sep_mask, batchUtt_in_dia_idx,
-                                      self.get_text_utt_max_lens, self.text_pretrained_model == 'roberta')
+                return plm(batch_text_input_ids, batch_text_input_mask)[0]
+        return plm(batch_text_input_ids, batch_text_input_mask)[0]                       # (B, T, plm_hidden); packed: (1, capacity, plm_hidden)
 
     def _pair(self, fa, fb, reads=()):
         """Run two independent sub-computations; with `self.pair_stream` set (by train_step.graph_multimodal) the first one

@@ -485,23 +485,32 @@ class VendorLinearFn(torch.autograd.Function):
         return dx, dw, db
 
 
-def plm_tail_fwd_raw(h2, r2, gamma, beta, eps, p, seed_i, seed_t, salt):
-    """fmmt_plm_dropadd_ln_fwd on (M, C) bf16 operands: returns (xsum, y)"""
+def plm_tail_fwd_raw(h2, r2, gamma, beta, eps, p, seed_i, seed_t, salt, row_map=None):
+    """fmmt_plm_dropadd_ln_fwd on (M, C) bf16 operands: returns (xsum, y).  row_map (int32 (M,), packed rows): fmmt_dropadd_ln_fwd_map -- row r draws
+    the dropout mask of row row_map[r]"""
     M, C = h2.shape
     xsum, y = torch.empty_like(h2), torch.empty_like(h2)
+    if row_map is not None:
+        check(_lib.load().fmmt_dropadd_ln_fwd_map(_lib.BF16, M, C, float(eps), _p(h2), _p(r2), _p(gamma), _p(beta), float(p), seed_i, _p(seed_t), int(salt), _p(xsum),
+                                                  _p(y), _p(row_map), _st()), f"fmmt_dropadd_ln_fwd_map(M={M},C={C})")
+        return xsum, y
     check(_lib.load().fmmt_plm_dropadd_ln_fwd(M, C, float(eps), _p(h2), _p(r2), _p(gamma), _p(beta), float(p), seed_i, _p(seed_t), int(salt), _p(xsum), _p(y), _st()),
           f"fmmt_plm_dropadd_ln_fwd(M={M},C={C})")
     return xsum, y
 
 
-def plm_tail_bwd_raw(dy2, xsum, gamma, eps, p, seed_i, seed_t, salt):
-    """fmmt_plm_dropadd_ln_bwd: returns (dx = the residual's gradient, dh = the dense output's, dgamma, dbeta, dbias)"""
+def plm_tail_bwd_raw(dy2, xsum, gamma, eps, p, seed_i, seed_t, salt, row_map=None):
+    """fmmt_plm_dropadd_ln_bwd (row_map: fmmt_dropadd_ln_bwd_map): returns (dx = the residual's gradient, dh = the dense output's, dgamma, dbeta, dbias)"""
     M, C = xsum.shape
     lib = _lib.load()
     dx, dh = torch.empty_like(xsum), torch.empty_like(xsum)
     dgamma, dbeta, dbias = torch.empty_like(gamma), torch.empty_like(gamma), torch.empty_like(gamma)
     nbytes = lib.fmmt_plm_dropadd_ln_bwd_workspace(M, C)
     ws = _ws(nbytes, xsum.device)
+    if row_map is not None:
+        check(lib.fmmt_dropadd_ln_bwd_map(_lib.BF16, M, C, eps, _p(dy2), _p(xsum), _p(gamma), p, seed_i, _p(seed_t), salt, _p(dx), _p(dh), _p(dgamma), _p(dbeta), _p(dbias),
+                                          _p(ws), nbytes, _p(row_map), _st()), f"fmmt_dropadd_ln_bwd_map(M={M},C={C})")
+        return dx, dh, dgamma, dbeta, dbias
     check(lib.fmmt_plm_dropadd_ln_bwd(M, C, eps, _p(dy2), _p(xsum), _p(gamma), p, seed_i, _p(seed_t), salt, _p(dx), _p(dh), _p(dgamma), _p(dbeta), _p(dbias), _p(ws), nbytes,
                                       _st()), f"fmmt_plm_dropadd_ln_bwd(M={M},C={C})")
     return dx, dh, dgamma, dbeta, dbias
@@ -551,16 +560,17 @@ class PlmFfnFn(torch.autograd.Function):
     of a GEMM and autograd's add.  Per layer and step 3 launches and two passes over the (tokens x 4096) matrix fewer."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, p, seed, salt):
+    def forward(ctx, x, w1, b1, w2, b2, gamma, beta, eps, p, seed, salt, row_map=None):
         pre = torch.nn.functional.linear(x, w1, b1)
         act = torch.nn.functional.gelu(pre)
         h = torch.nn.functional.linear(act, w2, b2)
         C = h.shape[-1]
         x2 = _c16(x.reshape(-1, C))
         seed_i, seed_t = _seed_args(seed)
-        xsum, y = plm_tail_fwd_raw(h.reshape(-1, C), x2, gamma.detach(), beta.detach(), eps, p, seed_i, seed_t, salt)
+        xsum, y = plm_tail_fwd_raw(h.reshape(-1, C), x2, gamma.detach(), beta.detach(), eps, p, seed_i, seed_t, salt, row_map)
         ctx.save_for_backward(x2, w1, w2, pre, act, xsum, gamma, seed_t)
         ctx.cfg = (float(eps), float(p), seed_i, int(salt))
+        ctx.row_map = row_map                                   # packed rows (TokenLayout.row_map, no gradient): the padded call's dropout mask
         return y.reshape(h.shape)
 
     @staticmethod
@@ -568,14 +578,14 @@ class PlmFfnFn(torch.autograd.Function):
         x2, w1, w2, pre, act, xsum, gamma, seed_t = ctx.saved_tensors
         eps, p, seed_i, salt = ctx.cfg
         M, C = xsum.shape
-        dx_ln, dh, dgamma, dbeta, db2 = plm_tail_bwd_raw(_c16(dy.reshape(M, C)), xsum, gamma.detach(), eps, p, seed_i, seed_t, salt)
+        dx_ln, dh, dgamma, dbeta, db2 = plm_tail_bwd_raw(_c16(dy.reshape(M, C)), xsum, gamma.detach(), eps, p, seed_i, seed_t, salt, ctx.row_map)
         act2, pre2 = act.reshape(M, -1), pre.reshape(M, -1)
         dact = dh.mm(w2)
         dw2 = dh.t().mm(act2)
         dpre, db1 = plm_gelu_bwd_colsum_raw(dact, pre2)
         dx = dx_ln.addmm_(dpre, w1) if ctx.needs_input_grad[0] else None      # in place: torch.addmm would first copy dx_ln into its result (a 4 MB memcpy node per layer)
         dw1 = dpre.t().mm(x2)
-        return (dx.reshape(dy.shape) if dx is not None else None), dw1, db1, dw2, db2, dgamma, dbeta, None, None, None, None
+        return (dx.reshape(dy.shape) if dx is not None else None), dw1, db1, dw2, db2, dgamma, dbeta, None, None, None, None, None
 
 
 class PlmSublayerTailFn(torch.autograd.Function):
@@ -586,13 +596,14 @@ class PlmSublayerTailFn(torch.autograd.Function):
     bf16 activations and parameters.  8 launches per sublayer and step become 6 of which 2 are small."""
 
     @staticmethod
-    def forward(ctx, x, res, weight, bias, gamma, beta, eps, p, seed, salt):
+    def forward(ctx, x, res, weight, bias, gamma, beta, eps, p, seed, salt, row_map=None):
         h = torch.nn.functional.linear(x, weight, bias)
         C = h.shape[-1]
         seed_i, seed_t = _seed_args(seed)
-        xsum, y = plm_tail_fwd_raw(h.reshape(-1, C), _c16(res.reshape(-1, C)), gamma.detach(), beta.detach(), eps, p, seed_i, seed_t, salt)
+        xsum, y = plm_tail_fwd_raw(h.reshape(-1, C), _c16(res.reshape(-1, C)), gamma.detach(), beta.detach(), eps, p, seed_i, seed_t, salt, row_map)
         ctx.save_for_backward(x, weight, xsum, gamma, seed_t)
         ctx.cfg = (float(eps), float(p), seed_i, int(salt))
+        ctx.row_map = row_map
         return y.reshape(h.shape)
 
     @staticmethod
@@ -600,10 +611,10 @@ class PlmSublayerTailFn(torch.autograd.Function):
         x, weight, xsum, gamma, seed_t = ctx.saved_tensors
         eps, p, seed_i, salt = ctx.cfg
         M, C = xsum.shape
-        dx, dh, dgamma, dbeta, dbias = plm_tail_bwd_raw(_c16(dy.reshape(M, C)), xsum, gamma.detach(), eps, p, seed_i, seed_t, salt)
+        dx, dh, dgamma, dbeta, dbias = plm_tail_bwd_raw(_c16(dy.reshape(M, C)), xsum, gamma.detach(), eps, p, seed_i, seed_t, salt, ctx.row_map)
         dxin = dh.reshape(dy.shape).matmul(weight) if ctx.needs_input_grad[0] else None
         dw = dh.t().mm(x.reshape(-1, x.shape[-1])) if ctx.needs_input_grad[2] else None
-        return dxin, dx.reshape(dy.shape), dw, dbias, dgamma, dbeta, None, None, None, None
+        return dxin, dx.reshape(dy.shape), dw, dbias, dgamma, dbeta, None, None, None, None, None
 
 
 class DropAddLnFn(Function):
@@ -683,9 +694,18 @@ class PlmSelfAttnFn(torch.autograd.Function):
     stream is the attention kernels' own (replayed in the backward, no mask stored)."""
 
     @staticmethod
-    def forward(ctx, x, wq, wk, wv, bq, bk, bv, w_all, b_all, num_heads, scale, p, seed, key_bias):
+    def forward(ctx, x, wq, wk, wv, bq, bk, bv, w_all, b_all, num_heads, scale, p, seed, key_bias, layout=None):
         qkv = torch.nn.functional.linear(x, w_all, b_all)
         seed_i, seed_t = _seed_args(seed)
+        ctx.layout = layout
+        if layout is not None:
+            # packed rows (TokenLayout; x (1, cap, E)): the kernels' ragged mode, bit for bit the padded call on the real rows -- no key bias is needed,
+            # a sequence's keys end where it ends
+            assert key_bias is None and x.shape[0] == 1 and x.shape[1] == layout.cap, (tuple(x.shape), layout.cap)
+            out, lse = mha_ragged_fwd_raw(qkv[0], layout, int(num_heads), float(scale), float(p), seed_i, seed_t)
+            ctx.save_for_backward(x, w_all, qkv, out, lse, seed_t, None)
+            ctx.cfg = (int(num_heads), float(scale), float(p), seed_i)
+            return out[None]
         if key_bias is not None:                                 # the kernels read it as a row-major fp32 (B, S) array
             key_bias = key_bias.detach().to(torch.float32).contiguous()
             assert key_bias.shape == x.shape[:2], f"key_bias must be (B, S) = {tuple(x.shape[:2])}, got {tuple(key_bias.shape)}"
@@ -699,12 +719,15 @@ class PlmSelfAttnFn(torch.autograd.Function):
         x, w_all, qkv, out, lse, seed_t, key_bias = ctx.saved_tensors
         num_heads, scale, p, seed_i = ctx.cfg
         E = w_all.shape[0] // 3
-        d = mha_packed_bm_bwd_raw(qkv, out, _c16(dout), lse, num_heads, scale, p, seed_i, seed_t, key_bias)
+        if ctx.layout is not None:
+            d = mha_ragged_bwd_raw(qkv[0], ctx.layout, out, _c16(dout[0]), lse, num_heads, scale, p, seed_i, seed_t)[None]
+        else:
+            d = mha_packed_bm_bwd_raw(qkv, out, _c16(dout), lse, num_heads, scale, p, seed_i, seed_t, key_bias)
         d2 = d.reshape(-1, 3 * E)
         dx = d.matmul(w_all) if ctx.needs_input_grad[0] else None
         dw = d2.t().mm(x.reshape(-1, x.shape[-1]))
         db = colsum_raw(d2)
-        return dx, dw[:E], dw[E:2 * E], dw[2 * E:], db[:E], db[E:2 * E], db[2 * E:], None, None, None, None, None, None, None
+        return dx, dw[:E], dw[E:2 * E], dw[2 * E:], db[:E], db[E:2 * E], db[2 * E:], None, None, None, None, None, None, None, None
 
 
 def mlp_fused_raw(x2, w1l, b1, w2l, b2, res2, rowscale, rows_per_scale, h_pre, h_act=None, dg=False):
@@ -1309,6 +1332,107 @@ def mha_packed_bm_fwd_raw(qkv, num_heads, scale, dropout_p, seed_i, seed_t, key_
 def mha_packed_bm_bwd_raw(qkv, out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias):
     """mha_packed_bwd_raw over a batch-major qkv (B, S, 3E): (B, S, 3E) = [dq | dk | dv]"""
     return mha_packed_bwd_raw(qkv, qkv.shape[1], qkv.shape[0], out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t, key_bias, batch_major=True)
+
+
+# ------------------------------------------------------------------------------------------------
+# the text encoder on real tokens only (include/fmmt_tokens.h)
+# ------------------------------------------------------------------------------------------------
+class TokenLayout:
+    """how the leading real tokens of a (B, T) padding mask lie in `cap` packed rows (fmmt_token_layout): seq_len / seq_off int32 (B,), len64 int64 (B,)
+    -- the counts pack_frames / unpack_rows take --, row_map int32 (cap,) = the padded-layout row of each packed row, counts int32 (2,) = [rows packed,
+    non-zeros of the mask]; all on the device, none of it read on the host"""
+
+    def __init__(self, B, T, cap, seq_len, seq_off, len64, row_map, counts):
+        self.B, self.T, self.cap = B, T, cap
+        self.seq_len, self.seq_off, self.len64, self.row_map, self.counts = seq_len, seq_off, len64, row_map, counts
+
+
+def token_layout_raw(mask, cap):
+    """fmmt_token_layout on a (B, T) mask (any dtype: non-zero = real token; converted to int32 with one launch unless it is int32 already)"""
+    _need_cuda(mask, "token_layout")
+    B, T = mask.shape
+    m = mask.detach()
+    m = m.contiguous() if m.dtype == torch.int32 else (m != 0).to(torch.int32)
+    dev, cap = m.device, int(cap)
+    i32 = torch.empty(2 * B + cap + 2, dtype=torch.int32, device=dev)          # one block: seq_len | seq_off | row_map | counts
+    len64 = torch.empty(B, dtype=torch.int64, device=dev)
+    lay = TokenLayout(B, T, cap, i32[:B], i32[B:2 * B], len64, i32[2 * B:2 * B + cap], i32[2 * B + cap:])
+    check(_lib.load().fmmt_token_layout(B, T, cap, _p(m), _p(lay.seq_len), _p(lay.seq_off), _p(len64), _p(lay.row_map), _p(lay.counts), _st()),
+          f"fmmt_token_layout(B={B},T={T},cap={cap})")
+    return lay
+
+
+def unpack_rows_raw(src, len64, B, L):
+    """fmmt_unpack_rows: (cap, ...) packed rows + int64 (B,) counts -> (B, L, ...), zeros wherever no packed row belongs"""
+    _need_cuda(src, "unpack_rows")
+    s = src.detach().contiguous()
+    row_bytes = s[0].numel() * s.element_size()
+    out = torch.empty((B, L) + tuple(s.shape[1:]), dtype=s.dtype, device=s.device)
+    check(_lib.load().fmmt_unpack_rows(B, L, s.shape[0], row_bytes, _p(s), _p(len64), _p(out), _st()),
+          f"fmmt_unpack_rows(B={B},L={L},cap={s.shape[0]},row_bytes={row_bytes})")
+    return out
+
+
+class PackRowsFn(Function):
+    """(B, T, ...) -> (cap, ...): every sequence's leading seq_len rows back to back, zeros behind (fmmt_pack_frames); backward: fmmt_unpack_rows"""
+
+    @staticmethod
+    def forward(ctx, x, lay):
+        ctx.lay = lay
+        return pack_frames(x, lay.len64, lay.cap)[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        lay = ctx.lay
+        return unpack_rows_raw(dy, lay.len64, lay.B, lay.T), None
+
+
+class UnpackRowsFn(Function):
+    """(cap, ...) -> (B, T, ...): the inverse of PackRowsFn, zeros at the padded positions (fmmt_unpack_rows); backward: fmmt_pack_frames"""
+
+    @staticmethod
+    def forward(ctx, x, lay):
+        ctx.lay = lay
+        return unpack_rows_raw(x, lay.len64, lay.B, lay.T)
+
+    @staticmethod
+    def backward(ctx, dy):
+        lay = ctx.lay
+        return pack_frames(dy, lay.len64, lay.cap)[0], None
+
+
+def pack_rows(x, lay):
+    return PackRowsFn.apply(x, lay)
+
+
+def unpack_rows(x, lay):
+    return UnpackRowsFn.apply(x, lay)
+
+
+def mha_ragged_fwd_raw(qkv, lay, num_heads, scale, dropout_p, seed_i, seed_t):
+    """fmmt_mha_fwd_ragged of self-attention over a packed projection (cap, 3E), rows [q | k | v].  Returns (out (cap, E), lse (B * heads * T,) in
+    the padded call's layout: entries of padded queries are not written)"""
+    E = qkv.shape[-1] // 3
+    cap = qkv.shape[0]
+    out = torch.empty((cap, E), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((lay.B * num_heads * lay.T,), dtype=torch.float32, device=qkv.device)
+    check(_lib.load().fmmt_mha_fwd_ragged(dtype_code(qkv.dtype) | _lib.RAGGED, lay.T, lay.B, E, num_heads, cap, _p(lay.seq_off), _p(lay.seq_len),
+                                          *_packed_qkv(qkv, E), scale, dropout_p, seed_i, _p(seed_t), _p(out), E, _p(lse), _st()),
+          f"fmmt_mha_fwd_ragged(T={lay.T},B={lay.B},E={E},heads={num_heads},rows={cap})")
+    return out, lse
+
+
+def mha_ragged_bwd_raw(qkv, lay, out, dout, lse, num_heads, scale, dropout_p, seed_i, seed_t):
+    """fmmt_mha_bwd_ragged of mha_ragged_fwd_raw: (cap, 3E) = [dq | dk | dv], zeros in the rows behind the last sequence"""
+    E = qkv.shape[-1] // 3
+    cap = qkv.shape[0]
+    dqkv = torch.empty_like(qkv)
+    dqp, dkp, dvp = _cols(dqkv, E, 3)
+    check(_lib.load().fmmt_mha_bwd_ragged(dtype_code(qkv.dtype) | _lib.RAGGED, lay.T, lay.B, E, num_heads, cap, _p(lay.seq_off), _p(lay.seq_len),
+                                          *_packed_qkv(qkv, E), scale, dropout_p, seed_i, _p(seed_t), _p(out), _p(dout), E, _p(lse), dqp, 3 * E, dkp, dvp,
+                                          3 * E, _st()),
+          f"fmmt_mha_bwd_ragged(T={lay.T},B={lay.B},E={E},heads={num_heads},rows={cap})")
+    return dqkv
 
 
 class MhaCoreFn(Function):

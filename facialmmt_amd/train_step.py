@@ -125,6 +125,91 @@ def frame_buckets(frame_capacity):
 
 
 # ------------------------------------------------------------------------------------------------
+# The text encoder on real tokens only (token_capacity on the target steps; _SeedBox PACK_NOTE): what the host decides per call.
+# ------------------------------------------------------------------------------------------------
+# Capacities are whole multiples of this many rows: the default capacity is the construction batch's token count rounded up to it.  Measured at
+# the benchmark shape (4 x 512 tokens, 1600 real; NOTES.md R13): 64 and 128 rows are 0.1 ms apart (inside the spread), 256 is 0.3 ms behind; 64 leaves the benchmark no filler row.
+TOKEN_GRANULE = 64
+
+_TOKEN_COUNTS = {}                                           # device masks: id(tensor) -> (weak reference to it, its version, (total, prefix))
+
+
+def count_tokens(mask):
+    """(real tokens, every row a prefix of ones) of a (B, T) padding mask, on the host.  A host tensor (or nested list) is read directly; a device
+    tensor costs ONE synchronisation per (tensor object, version), so a loop that hands over the same unmodified tensor every step never waits.  (The
+    object, held weakly, and not its address: the caching allocator gives a new mask the address of a freed one.)"""
+    m = torch.as_tensor(mask)
+    if m.dim() != 2:
+        raise ValueError(f"the text padding mask must be (B, T), got {tuple(m.shape)}")
+    key = None
+    if m.is_cuda:
+        key = id(m)
+        hit = _TOKEN_COUNTS.get(key)
+        if hit is not None and hit[0]() is m and hit[1] == m._version:
+            return hit[2]
+    real = m != 0
+    lens = real.sum(1)
+    prefix = (real == (torch.arange(m.shape[1], device=m.device)[None, :] < lens[:, None])).all()
+    total, ok = torch.stack([lens.sum(), prefix.to(lens.dtype)]).tolist()
+    out = (int(total), bool(ok))
+    if key is not None:
+        if len(_TOKEN_COUNTS) > 64:
+            _TOKEN_COUNTS.clear()
+        import weakref
+        _TOKEN_COUNTS[key] = (weakref.ref(m), m._version, out)
+    return out
+
+
+def default_token_capacity(mask, granule=None):
+    """the capacity a step derives from its construction batch: the real tokens rounded up to TOKEN_GRANULE; 0 (= the padded path) for a mask with
+    a hole, without a real token, or whose rounded count reaches B * T"""
+    total, prefix = count_tokens(mask)
+    g = int(granule or TOKEN_GRANULE)
+    cap = (total + g - 1) // g * g
+    B, T = torch.as_tensor(mask).shape
+    return cap if prefix and 0 < total and cap < B * T else 0
+
+
+def token_box(mm):
+    """the _SeedBox of the multimodal model's text encoder when that encoder can run on packed rows (fuse_text_encoder packed every attention
+    module of a bf16 encoder stack), else None"""
+    plm = getattr(mm, "roberta", None) if getattr(mm, "text_pretrained_model", "") == "roberta" else getattr(mm, "bert", None)
+    box = getattr(plm, "_fmmt_box", None)
+    if box is None or not box.all_attention_fused or not PLM_FUSE_ATTN or next(plm.parameters()).dtype != torch.bfloat16:
+        return None
+    return box
+
+
+class _text_rows:
+    """`mm.text_token_capacity = rows` for the length of ONE forward of the model, 0 behind it whatever happens inside: whoever else calls the model
+    (an evaluation step, whose masks nobody checks on the host) sees the padded layout"""
+
+    def __init__(self, mm, rows):
+        self.mm, self.rows = mm, int(rows or 0)
+
+    def __enter__(self):
+        self.mm.text_token_capacity = self.rows
+
+    def __exit__(self, *exc):
+        self.mm.text_token_capacity = 0
+        return False
+
+
+def token_fit(mask, capacity):
+    """Does this batch run on packed rows?  False: token packing is off (capacity 0) or the mask is not a prefix of ones per row (the padded path
+    computes such a mask correctly).  A prefix mask with more real tokens than `capacity`: ValueError, as check_frame_total for frames -- before
+    anything is launched."""
+    if not capacity:
+        return False
+    total, prefix = count_tokens(mask)
+    if not prefix:
+        return False
+    if total > capacity:
+        raise ValueError(f"the batch holds {total} text tokens, the step was built for token_capacity={capacity}")
+    return True
+
+
+# ------------------------------------------------------------------------------------------------
 # A short last batch of an epoch behind a captured batch shape (pad_rows=True on the graphed steps).  PAD_NOTE: the rule for what a padded row
 # holds, stated once.  Every padded row is a computation that can occur for a real utterance -- no kernel meets a degenerate case (a row whose
 # masks are all zero gives NaN in the pooling head's softmax and in the text encoder's attention) -- and its label is -100, F.cross_entropy's
@@ -330,7 +415,7 @@ class TargetStep(StepState):
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "target", ("swin", "mm"), "trg_accumulation_steps"
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, autocast_dtype=None, ddp_model=None, averager=None,
-                 discarded_swin_gradients="compute", frame_capacity=None, color_jitter=None):
+                 discarded_swin_gradients="compute", frame_capacity=None, color_jitter=None, token_capacity=None):
         """Data parallel: pass `averager` (parallel.GradientAverager over the multimodal parameters) or, alternatively,
         `ddp_model` (the module wrapped by torch's DistributedDataParallel).
         `color_jitter` (an augment.ColorJitter; None: no augmentation): the MELD train transform (utils/dataset.py:35-39,62-63) on the uint8 frames,
@@ -340,7 +425,15 @@ class TargetStep(StepState):
         (B, Lv, ...), and the step packs them on the device into `frame_capacity` rows (ops.pack_frames), runs Swin on all of them with the
         head's BatchNorm over the real ones and filters with the same row count -- GraphedTargetStep(frame_capacity=...) launch by launch.  An
         ascending tuple of capacities: every batch is packed into the smallest that holds it (`frame_bucket`: num_imgs as a list or CPU tensor; a
-        device tensor takes the largest); `capacity` is the one the last call ran in, `replays` counts the calls per capacity."""
+        device tensor takes the largest); `capacity` is the one the last call ran in, `replays` counts the calls per capacity.
+        `token_capacity` (PACK_NOTE): the text encoder's layers run on the real tokens packed into that many rows.  None (default): every call takes
+        its own batch's count rounded up to TOKEN_GRANULE (nothing here has a captured shape); an integer: that many rows, more real tokens raise
+        ValueError; 0: the padded layout.  A mask with a hole takes the padded layout.  `token_rows`: what the last call ran with (0: padded).
+        Not under `ddp_model` (torch's DDP calls the module through its own forward: the padded layout)."""
+        self.token_capacity = None if token_capacity is None else int(token_capacity)
+        if self.token_capacity is not None and self.token_capacity < 0:
+            raise ValueError("token_capacity: a number of rows, 0 (padded layout) or None (per batch)")
+        self.token_rows = 0
         self.capacities = frame_buckets(frame_capacity)
         self.frame_capacity = None if self.capacities is None else self.capacities[-1]
         self.capacity, self.replays = None, {c: 0 for c in self.capacities or ()}
@@ -393,6 +486,15 @@ class TargetStep(StepState):
         from .parallel import GradientAverager, accumulate
         if self.color_jitter is not None:
             _need_u8_frames(frames)                          # ValueError before anything is launched
+        if self.mm_call is not self.mm or token_box(self.mm) is None:
+            if self.token_capacity:
+                raise ValueError("token_capacity: needs the fused bf16 text encoder, called without torch's DistributedDataParallel")
+            rows = 0
+        elif self.token_capacity is None:
+            rows = default_token_capacity(attn_mask)
+        else:
+            rows = self.token_capacity if token_fit(attn_mask, self.token_capacity) else 0      # ValueError before anything is launched
+        self.token_rows = rows
         n_valid, swin_kw = None, {}
         if self.capacities is not None:
             cap = frame_bucket(num_imgs, frames.shape[1], self.capacities)     # ValueError before anything is launched
@@ -406,11 +508,12 @@ class TargetStep(StepState):
         last = self.i_batch % args.trg_accumulation_steps == 0
         if getattr(self.mm, "text_stream", None) is not None:
             # start the text branch on its own stream before the Swin forward is enqueued (models.launch_text)
-            if self.autocast_dtype is not None:
-                with torch.autocast("cuda", dtype=self.autocast_dtype):
+            with _text_rows(self.mm, rows):
+                if self.autocast_dtype is not None:
+                    with torch.autocast("cuda", dtype=self.autocast_dtype):
+                        self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
+                else:
                     self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
-            else:
-                self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
         if self.color_jitter is not None:                   # one record per frame Swin runs on (packed: per slot of the capacity), drawn just ahead of Swin
             self.last_jitter = swin_kw["jitter"] = self.color_jitter.draw(frames.shape[0], frames.device)
         if self.skip_swin_bwd:
@@ -424,11 +527,12 @@ class TargetStep(StepState):
         # gradient exchange only on the last micro-step of the window; torch's DDP decides in its FORWARD whether the
         # coming backward synchronises, so the no_sync context has to cover the forward as well
         with accumulate(self.exchange, last):
-            if self.autocast_dtype is not None:
-                with torch.autocast("cuda", dtype=self.autocast_dtype):
+            with _text_rows(self.mm, rows):
+                if self.autocast_dtype is not None:
+                    with torch.autocast("cuda", dtype=self.autocast_dtype):
+                        logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
+                else:
                     logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
-            else:
-                logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
             mark("multimodal_fwd")
             loss = F.cross_entropy(logits.float(), labels) / args.trg_accumulation_steps
             loss.backward()
@@ -524,6 +628,7 @@ class _SeedBox:
 
     def __init__(self):
         self.t = None
+        self.all_attention_fused = False
         self.words = 1            # word 0: the sublayer tails (each adds its salt); word 1 + i: attention module i (its kernels take no salt)
         # the attention mask the caller handed the encoder, recorded by its pre-hook for the length of one forward: (mask: None or (batch, keys)
         # padding mask, its per-key logit bias once _fused_attention made it), or None = no forward of the encoder in progress or a mask of another
@@ -531,6 +636,48 @@ class _SeedBox:
         # A layer forward re-run after the model's forward returned (activation-checkpoint recomputation in the backward) finds no record and
         # would take the stock attention where the original forward took the fused one: a model with gradient checkpointing on records nothing
         self.mask = None
+        # PACK_NOTE.  Running the layers on real tokens only.  `capacity` (0: off; set by the caller for the forwards it wants packed, e.g.
+        # MultiModalTransformerForClassification.text_branch from `text_token_capacity`): with a (batch, keys) padding mask whose rows are prefixes of
+        # ones, the hook in front of the encoder stack (encoder_pre_hook) packs the embedding output's real rows into (1, capacity, E) -- the
+        # embeddings themselves and their dropout stream stay on the padded layout --, records the ops.TokenLayout in `packed` for the length of the
+        # forward and drops the mask; attention then runs the kernels' ragged mode, the tails and the feed-forward node draw the padded call's dropout
+        # mask through the layout's row map, and the model hands back (1, capacity, E): rows of the real tokens, sequence by sequence, zeros (and
+        # zero gradients) behind.  `layout_out` keeps the layout of the last packed forward for the caller's ops.unpack_rows (take_layout).  The
+        # CALLER vouches for the mask: a hole or more tokens than the capacity is not detected here (the steps check on the host, train_step.token_fit;
+        # on the device the lengths are cut to the capacity, so nothing is read or written out of bounds -- the result is then simply wrong).
+        self.capacity = 0
+        self.packed = None
+        self.layout_out = None
+        self.packed_forwards = 0                            # forwards that ran packed: a step that asked for packing checks that it happened
+
+    def take_layout(self):
+        """the layout of the forward that just returned if it ran packed (once), else None"""
+        lay, self.layout_out = self.layout_out, None
+        return lay
+
+    def encoder_pre_hook(self, mod, args, kwargs):
+        """forward pre-hook of the encoder STACK (plm.encoder): PACK_NOTE.  Packs only inside a forward of the model that recorded a 2-d padding mask."""
+        self.packed = None
+        rec, cap = self.mask, int(self.capacity or 0)
+        if cap <= 0 or rec is None or rec[0] is None or not args or not torch.is_tensor(args[0]) or not self.all_attention_fused:
+            return None
+        x = args[0]
+        B, T = rec[0].shape
+        if x.dim() != 3 or tuple(x.shape[:2]) != (B, T) or not x.is_cuda or x.dtype != torch.bfloat16 or not PLM_FUSE_ATTN or not _fusable_now():
+            return None
+        if cap > B * T or (x.shape[-1] * x.element_size()) % 16:
+            return None
+        from . import ops
+        lay = ops.token_layout_raw(rec[0], cap)
+        self.packed = self.layout_out = lay
+        self.packed_forwards += 1
+        kwargs = dict(kwargs)
+        rest = list(args[1:])
+        if "attention_mask" in kwargs:
+            kwargs["attention_mask"] = None                 # a sequence's keys end where it ends: the ragged kernels need no bias
+        elif rest:
+            rest[0] = None
+        return (ops.pack_rows(x, lay)[None],) + tuple(rest), kwargs
 
     def draw(self, device):
         self.t = torch.randint(0, 2 ** 62, (self.words,), dtype=torch.int64, device=device)
@@ -540,6 +687,7 @@ class _SeedBox:
         if mod.training:
             self.draw(next(mod.parameters()).device)
         mask = kwargs["attention_mask"] if "attention_mask" in kwargs else (args[1] if len(args) > 1 else None)
+        self.packed = self.layout_out = None
         if getattr(mod, "is_gradient_checkpointing", False):
             self.mask = None
         else:
@@ -547,6 +695,13 @@ class _SeedBox:
 
     def post_hook(self, mod, args, kwargs, out):
         self.mask = None
+        self.packed = None
+
+
+def _row_map(box, x):
+    """PACK_NOTE: the row map of the packed forward in progress when x is its (1, capacity, E) rows, else None"""
+    lay = box.packed
+    return lay.row_map if lay is not None and x.dim() == 3 and x.shape[0] == 1 and x.shape[1] == lay.cap else None
 
 
 def _sublayer_tail_forward(self, hidden_states, input_tensor):
@@ -560,7 +715,7 @@ def _sublayer_tail_forward(self, hidden_states, input_tensor):
         return self._fmmt_stock_forward(hidden_states, input_tensor)
     from . import ops
     return ops.PlmSublayerTailFn.apply(hidden_states, input_tensor, d.weight, d.bias, ln.weight, ln.bias, ln.eps, p,
-                                       box.t if p > 0.0 else 0, self._fmmt_salt)
+                                       box.t if p > 0.0 else 0, self._fmmt_salt, _row_map(box, hidden_states))
 
 
 def _fused_ffn_chunk(self, attention_output):
@@ -579,7 +734,8 @@ def _fused_ffn_chunk(self, attention_output):
             or d1.weight.shape[0] % 8 or d1.weight.shape[0] > 8192 or d1.weight.shape[1] != d2.weight.shape[0] or (p > 0.0 and box.t is None)):
         return self._fmmt_stock_ffn(attention_output)
     from . import ops
-    return ops.PlmFfnFn.apply(x, d1.weight, d1.bias, d2.weight, d2.bias, ln.weight, ln.bias, ln.eps, p, box.t if p > 0.0 else 0, out._fmmt_salt)
+    return ops.PlmFfnFn.apply(x, d1.weight, d1.bias, d2.weight, d2.bias, ln.weight, ln.bias, ln.eps, p, box.t if p > 0.0 else 0, out._fmmt_salt,
+                              _row_map(box, x))
 
 
 def _fused_embedding_forward(self, input):
@@ -614,12 +770,19 @@ def _packed_qkv_forward(self, hidden_states, *args, **kwargs):
     # (round-5 ADVICE).  transformers passes these by keyword or as the positional slots behind attention_mask / head_mask
     cross = (getattr(self, "is_cross_attention", False) or any(kwargs.get(k) is not None for k in ("encoder_hidden_states", "past_key_value", "past_key_values"))
              or any(torch.is_tensor(a) and a.dim() == 3 and a.shape[-1] == hidden_states.shape[-1] for a in args[2:]))
+    packed = getattr(self._fmmt_seed, "packed", None) is not None
     if not ok or cross:
+        if packed:
+            raise RuntimeError("text encoder on packed rows (PACK_NOTE): this attention module cannot take the fused path, and the stock attention "
+                               "would mix the sequences; build the step with token_capacity=0")
         return self._fmmt_stock_forward(hidden_states, *args, **kwargs)
     from . import ops
     fused = _fused_attention(self, hidden_states, args, kwargs, w, b)
     if fused is not None:
         return fused
+    if packed:
+        raise RuntimeError("text encoder on packed rows (PACK_NOTE): the in-tree attention kernels do not apply to this module, and the stock "
+                           "attention would mix the sequences; build the step with token_capacity=0")
     yq, yk, yv = ops.PlmQkvFn.apply(hidden_states, q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, w, b)
     saved = (self.query, self.key, self.value)
     try:                                                     # the stock forward calls self.query(x) ...: hand it the projections already made
@@ -655,7 +818,11 @@ def _fused_attention(self, hidden_states, args, kwargs, w, b):
                              or mask.shape[2] not in (1, S)):
         return None
     key_bias = None
-    if rec[0] is not None:
+    lay = box.packed
+    if lay is not None:                                     # PACK_NOTE: (1, capacity, E) rows, the mask dropped by encoder_pre_hook
+        if mask is not None or B != 1 or S != lay.cap:
+            return None
+    elif rec[0] is not None:
         if rec[0].shape != (B, S):
             return None
         if rec[1] is None:                                  # once per forward of the encoder, not once per layer
@@ -669,7 +836,7 @@ def _fused_attention(self, hidden_states, args, kwargs, w, b):
     scale = float(getattr(self, "scaling", 64 ** -0.5))
     from . import ops
     q, k, v = self.query, self.key, self.value
-    out = ops.PlmSelfAttnFn.apply(hidden_states, q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, w, b, nH, scale, p, seed, key_bias)
+    out = ops.PlmSelfAttnFn.apply(hidden_states, q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, w, b, nH, scale, p, seed, key_bias, lay)
     return out, None
 
 
@@ -747,6 +914,13 @@ def fuse_text_encoder(plm, tails: bool = True, qkv: bool = True):
     if n_tail or n_qkv:
         plm.register_forward_pre_hook(box.pre_hook, with_kwargs=True)
         plm.register_forward_hook(box.post_hook, with_kwargs=True, always_call=True)
+        # PACK_NOTE: the pack sits in front of the encoder stack, and only a stack whose every attention module was packed above may run on packed rows
+        stack = getattr(plm, "encoder", None)
+        n_attn = sum(1 for _, m in plm.named_modules() if type(m).__name__.endswith("SelfAttention"))
+        box.all_attention_fused = bool(n_qkv) and n_qkv == n_attn
+        if isinstance(stack, torch.nn.Module) and stack is not plm:
+            stack.register_forward_pre_hook(box.encoder_pre_hook, with_kwargs=True)
+        plm._fmmt_box = box
     return n_tail, n_qkv
 
 
@@ -1560,7 +1734,7 @@ class GraphedTargetStep(StepState):
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
                  swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None,
-                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None, grad_report: bool = False):
+                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None, grad_report: bool = False, token_capacity=None):
         """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
@@ -1605,11 +1779,41 @@ class GraphedTargetStep(StepState):
         62-63) inside the uint8 pre-step.  The draw of the per-frame table is PART of every capture in front of Swin's forward (every capacity's, and
         graph S of pipeline_swin): one torch.rand on the device generator and elementwise launches, so every replay jitters anew and a resumed
         generator walks the same tables.  With a frame capacity the table has that many records (padded slots are jittered like any bytes: nothing
-        reads them).  `last_jitter`: the table of the last Swin forward replayed (device, int32 (frames, 8)).  Frames must be uint8 (ValueError)."""
+        reads them).  `last_jitter`: the table of the last Swin forward replayed (device, int32 (frames, 8)).  Frames must be uint8 (ValueError).
+        `token_capacity` (PACK_NOTE; the default single-graph mode and the two-piece mode of an active averager, with or without frame capacities):
+        the text encoder's layers and text_linear run on the real tokens of the batch packed into that many rows -- a fixed number, the captured
+        shape.  None (default): the sample batch's real tokens rounded up to TOKEN_GRANULE (0 when its mask has a hole, or under pipeline_swin /
+        branch_graphs / fork_streams); an integer: that many rows (NotImplementedError with those three modes); 0: the padded layout, the captures
+        of before.  With packing on, every forward/backward graph is captured TWICE, on packed rows and on the padded layout (a pool each; the
+        update graph, the flat buffers and the static inputs are shared): a call counts the real tokens of its mask on the host (count_tokens: a
+        device mask costs one synchronisation per new tensor or version) and replays the packed capture when every row of the mask is a prefix
+        of ones, the padded one when it has a hole; more real tokens than the capacity: ValueError before any copy or launch.  The setting holds
+        for every frame capacity.  `token_capacity`: the rows; `token_replays`: {"packed": calls, "padded": calls}; `twin_capture_bytes` /
+        `twin_capture_reserved_bytes`: {frame capacity, or None without one: what the padded twin's capture added}, as `capture_bytes` /
+        `capture_reserved_bytes` say it of the packed captures -- a twin costs about what its packed capture costs, in memory and in capture time.
+        The hand-over's pinned capture tables are sized for both sets (two per frame capacity)."""
         from . import ops
         from .parallel import GradientAverager
         if discarded_swin_gradients not in ("compute", "skip"):
             raise ValueError("discarded_swin_gradients: 'compute' or 'skip'")
+        other_mode = bool(pipeline_swin or branch_graphs or fork_streams)
+        box = token_box(multimodal_model)
+        if token_capacity is None:
+            token_capacity = 0 if (other_mode or box is None) else default_token_capacity(batch[1])
+        self.token_capacity = int(token_capacity)
+        if self.token_capacity and box is None:
+            raise ValueError("token_capacity: the text encoder is not the fused bf16 encoder (MasterWeights / fuse_text_encoder) that can run on packed rows")
+        if self.token_capacity < 0:
+            raise ValueError("token_capacity: a number of rows, 0 (padded layout) or None (from the sample batch)")
+        if self.token_capacity and other_mode:
+            raise NotImplementedError("token_capacity: the default single-graph mode, or the two-piece mode of an active gradient exchange (not with "
+                                      "pipeline_swin / branch_graphs / fork_streams)")
+        if self.token_capacity and not token_fit(batch[1], self.token_capacity):      # ValueError: the sample itself does not fit
+            raise ValueError("token_capacity: the sample batch's text mask has a hole; the captures need a sample that packs")
+        self.token_replays, self._padded_graphs = {"packed": 0, "padded": 0}, {}
+        self.twin_capture_bytes, self.twin_capture_reserved_bytes = {}, {}
+        self._rows_now = self.token_capacity                # what the pass in progress (warm-up, capture) runs the text branch with: _text_rows sets it on
+                                                            # the model for the length of that forward only, so nobody else who calls the model ever packs
         self.skip_swin_bwd = discarded_swin_gradients == "skip"
         self.pipeline = bool(pipeline_swin)
         self.branches = bool(branch_graphs)                 # BRANCH_NOTE below
@@ -1663,7 +1867,7 @@ class GraphedTargetStep(StepState):
         # Captures without (pad_rows and an active exchange) have no such word and keep their launch sequence.
         self.row_weight = torch.ones((), dtype=torch.float32, device=dev) if (self.pad_rows and flat.active) else None
         self.tail = tail = FlatGradientTail(flat, optimizer, args.clip, args.trg_accumulation_steps > 1, masters=masters, exchanging=bool(flat.active),
-                                            capture_tables=max(4, len(self.capacities or ())), monitor=self.monitor, report=self.grad_report)
+                                            capture_tables=max(4, (2 if self.token_capacity else 1) * len(self.capacities or ())), monitor=self.monitor, report=self.grad_report)
         self.flat, self.flat_view_of, self.pairs, self.fused, self.handover = tail.flat, tail.flat_view_of, tail.pairs, tail.fused, tail.handover
         self.mm.text_stream = None
         # inside ONE graph the fork / join below become parallel branches; which hardware queue the branches replay on is the
@@ -1690,9 +1894,18 @@ class GraphedTargetStep(StepState):
             if multi:
                 self._use_capacity(c, batch)
             with warmup_undone(snap, dev, cap, tail.undo_warmup):
+                self._rows_now = self.token_capacity
+                ran = box.packed_forwards if box is not None else 0
                 for _ in range(warmup_iters):
                     self._fwd_bwd()
                     tail.update()
+                if self.token_capacity and warmup_iters and box.packed_forwards == ran:
+                    raise RuntimeError("token_capacity: the text encoder's forward did not run on packed rows (PACK_NOTE): no quiet padded capture")
+                if self.token_capacity and warmup_iters:       # the padded twin's shapes have lazy initialisations of their own
+                    self._rows_now = 0
+                    self._fwd_bwd()
+                    tail.update()
+                    self._rows_now = self.token_capacity
                 self.swin.zero_grad(set_to_none=True)
         del snap
         # -- capture
@@ -1829,7 +2042,32 @@ class GraphedTargetStep(StepState):
             if not multi:
                 with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
                     tail.update()
+            if self.token_capacity:
+                # the padded twins (token_capacity above): per frame capacity the same forward/backward with the text encoder on the padded layout,
+                # in a pool of its own for the reason of BUCKET_NOTE; no Swin gradient of an earlier capture may be left to add into
+                self._rows_now = 0
+                for c in self.capacities or (None,):
+                    if multi:
+                        self._use_capacity(c, batch)
+                    self.swin.zero_grad(set_to_none=True)
+                    g1, g2 = torch.cuda.CUDAGraph(), (torch.cuda.CUDAGraph() if self.split else None)
+                    before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
+                    if self.split:
+                        with torch.cuda.graph(g1, stream=cap):
+                            loss, new_mask, swin_out = self._fwd_bwd_multimodal()
+                        with torch.cuda.graph(g2, pool=g1.pool(), stream=cap):
+                            self._bwd_swin(swin_out)
+                        del swin_out
+                    else:
+                        with torch.cuda.graph(g1, stream=cap):
+                            loss, new_mask = self._fwd_bwd()
+                    self._padded_graphs[c if multi else None] = (g1, loss, new_mask, g2)
+                    self.twin_capture_bytes[c] = torch.cuda.memory_allocated(dev) - before[0]
+                    self.twin_capture_reserved_bytes[c] = torch.cuda.memory_reserved(dev) - before[1]
+                    _KEEP_GRAPHS.append((g1, g2))
+                self._rows_now = self.token_capacity
         _KEEP_GRAPHS.append((self.graph_a, self.graph_a2, self.graph_b))
+        self._own_outputs = (self.loss, self.new_mask)     # the packed (or only) capture's outputs: a call of a padded twin swaps its own in
         if multi:
             self._use_capacity(self.capacities[-1], batch)  # the sample's own counts (they fit the largest capacity) back in the static input
         self.swin.zero_grad(set_to_none=True)              # drop the references; the graph's pool keeps the buffers
@@ -1894,7 +2132,7 @@ class GraphedTargetStep(StepState):
             self.mm_shadows.refresh()
         import contextlib
         ac = (lambda: torch.autocast("cuda", dtype=self.autocast_dtype)) if self.autocast_dtype is not None else contextlib.nullcontext
-        with ac():
+        with ac(), _text_rows(self.mm, self._rows_now):
             return self.mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
 
     def _fusion_fwd_bwd(self, feat, tmask, preds):
@@ -2021,7 +2259,7 @@ class GraphedTargetStep(StepState):
 
             def launch_text(*_):
                 self.text_stream.wait_event(fork_ev)
-                with torch.cuda.stream(self.text_stream), ac():
+                with torch.cuda.stream(self.text_stream), ac(), _text_rows(mm, self._rows_now):
                     box["out"] = mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
 
             where = self.TEXT_FORK_AT if preds is None and not self.skip_swin_bwd else "start"
@@ -2063,7 +2301,8 @@ class GraphedTargetStep(StepState):
                                              self.frame_counts if self.frame_capacity is not None else None)
         with ac():
             if pending is None:
-                pending = mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
+                with _text_rows(mm, self._rows_now):
+                    pending = mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
             else:
                 main.wait_stream(self.text_stream)         # join
                 for t in pending:
@@ -2182,11 +2421,16 @@ class GraphedTargetStep(StepState):
         if self.pad_rows and b != rows:
             batch = pad_target_batch(batch, rows)           # ValueError for b == 0 or b > rows, before any copy or launch
         graph_a, graph_a2 = self.graph_a, self.graph_a2
+        packed = token_fit(batch[1], self.token_capacity)   # ValueError before any copy or launch; False: padding off, or a mask with a hole
+        c = None
         if self.capacities is not None:
             # the smallest capacity that holds the batch (host counts; a device tensor: the largest, unread); ValueError before any copy or launch
             c = frame_bucket(batch[9], self.static[8].shape[1], self.capacities)
             if self._graphs:
                 graph_a, graph_a2 = self._graphs[c][0], self._graphs_a2.get(c)
+        twin = self._padded_graphs[c if self._graphs else None] if (self.token_capacity and not packed) else None     # keyed as _graphs is
+        if twin is not None:
+            graph_a, graph_a2 = twin[0], twin[3]
         copy_into_static(self.static, batch, "GraphedTargetStep")
         if self.row_weight is not None:
             self.row_weight.fill_(weight)                   # a device fill: no host synchronisation
@@ -2198,6 +2442,12 @@ class GraphedTargetStep(StepState):
             self.replays[c] += 1
             if self._graphs:
                 _, self.loss, self.new_mask = self._graphs[c]   # every graph A has its own outputs
+        if self.token_capacity:
+            self.token_replays["packed" if packed else "padded"] += 1
+            if twin is not None:
+                self.loss, self.new_mask = twin[1], twin[2]
+            elif not self._graphs:
+                self.loss, self.new_mask = self._own_outputs
         self.i_batch += 1
         last = self.i_batch % self.args.trg_accumulation_steps == 0
         if last:

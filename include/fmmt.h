@@ -535,6 +535,8 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_groups.h"
 /* Per-tensor statistics over the optimizer's descriptor table, and the snapshot of a bad update (fmmt_table_stats): likewise, held to _lib.STATS_SIGNATURES. */
 #include "fmmt_stats.h"
+/* The text encoder on real tokens only (token layout of a padding mask, the unpack of packed rows, the attention core's ragged mode, the sublayer tails' row map): likewise, held to _lib.TOKENS_SIGNATURES. */
+#include "fmmt_tokens.h"
 
 #ifdef __cplusplus
 }
