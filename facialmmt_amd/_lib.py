@@ -192,6 +192,15 @@ TOKENS_SIGNATURES = {
     "fmmt_dropadd_ln_fwd_map": (_i, [_i, _i, _i, _f, _p, _p, _p, _p, _f, _u64, _p, _u64, _p, _p, _p, _p]),
     "fmmt_dropadd_ln_bwd_map": (_i, [_i, _i, _i, _f, _p, _p, _p, _f, _u64, _p, _u64, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
 }
+# include/fmmt_loss.h, one to one: a fourteenth table and header -- the class-weighted, label-smoothed cross-entropy of (B, NL) logits, one launch per
+# direction, and the pooling head's _rows pair with that loss (a float `den` word for the int row count) (tests/test_criterion_cpu.py holds table, header and library together)
+LOSS_SIGNATURES = {
+    "fmmt_ce_fwd": (_i, [_i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _p]),
+    "fmmt_ce_bwd": (_i, [_i, _i, _i, _p, _i, _p, _p, _f, _p, _p, _p, _i, _p]),
+    "fmmt_pool_head_fwd_crit": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _u64, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _sz, _p]),
+    "fmmt_pool_head_bwd_crit": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+}
+CE_MAXNL, CE_MAXB = 8, 65536          # include/fmmt_loss.h: the limits of fmmt_ce_fwd / _bwd
 RAGGED = 0x800          # include/fmmt_tokens.h FMMT_RAGGED: the dtype flag fmmt_mha_fwd_ragged / _bwd_ragged ask for
 
 FMMT_EINVAL, FMMT_EALIGN, FMMT_EWORKSPACE = -1, -2, -3
@@ -214,7 +223,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + list(TOKENS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + list(TOKENS_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -21,6 +21,8 @@
 // The _rows entry points (include/fmmt_pool_head_rows.h) run the SAME four kernels with a divisor source: n_rows != NULL makes the forward's finishing launch count
 // the rows whose label lies in [0, NL), store the count and divide by it, and makes the backward read that word on the device instead of dividing by B.
 // n_rows == NULL is the B-divisor pair.  Every label valid: count == B, the same division, the same bits.
+// The _crit entry points (include/fmmt_loss.h) instantiate the finishing launch and the token launch with CRIT: the row loss and d(logits) of the
+// class-weighted, label-smoothed cross-entropy, the divisor a float device word (sum of w[label]).  No weights and eps == 0: the bits of the _rows pair.
 // FMMT_BF16: h / ph / dh / dph bf16, everything else and all arithmetic fp32;  FMMT_F32: the same template, nothing rounded.
 #include "fmmt_common.h"
 #include "../../include/fmmt.h"
@@ -163,13 +165,15 @@ __global__ __launch_bounds__(PH_THREADS) void ph_fwd_partial_kernel(int L, int H
     }
 }
 
+template <bool CRIT>
 __global__ __launch_bounds__(PH_FIN_WAVES * 64) void ph_fwd_finish_kernel(int B, int L, int H, int NL, int NS, const float* __restrict__ ml,
                                                                           const float* __restrict__ ppool, const float* __restrict__ W,
                                                                           const float* __restrict__ bias, const long long* __restrict__ labels, float p,
                                                                           unsigned long long seed_i, const unsigned long long* __restrict__ seed_ptr,
                                                                           float* __restrict__ alpha, float* __restrict__ pooled, float* __restrict__ keep,
                                                                           float* __restrict__ logits, float* __restrict__ loss,
-                                                                          int* __restrict__ n_rows) {
+                                                                          int* __restrict__ n_rows, const float* __restrict__ class_w, float eps,
+                                                                          float* __restrict__ den) {
     constexpr int KMAX = PH_MAXH / 64;
     __shared__ float rl[PH_MAXB];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -240,7 +244,20 @@ __global__ __launch_bounds__(PH_FIN_WAVES * 64) void ph_fwd_finish_kernel(int B,
             vl = n == (int)label && label >= 0 && label < NL ? lg[n] : vl;
             if (lane == n && n < NL) logits[(size_t)b * NL + n] = lg[n];
         }
-        if (lane == 0) rl[b] = lse - vl;
+        float row = lse - vl;
+        if constexpr (CRIT) {                               // include/fmmt_loss.h: (1 - eps) w[y] (-log p_y) + eps / NL sum_c w_c (-log p_c); 0 without a label
+            const bool valid = label >= 0 && label < NL;
+            float wy = 0.f, t2 = 0.f;
+#pragma unroll
+            for (int n = 0; n < PH_MAXNL; ++n) {
+                const float wn = n < NL ? (class_w != nullptr ? class_w[n] : 1.f) : 0.f;
+                wy = n == (int)label ? wn : wy;
+                t2 += n < NL ? wn * (lse - lg[n]) : 0.f;
+            }
+            row = valid ? (1.0f - eps) * wy * row : 0.f;
+            if (valid && eps > 0.f) row = fmaf(eps / (float)NL, t2, row);
+        }
+        if (lane == 0) rl[b] = row;
     }
     __syncthreads();
     if (wave == 0) {
@@ -248,7 +265,7 @@ __global__ __launch_bounds__(PH_FIN_WAVES * 64) void ph_fwd_finish_kernel(int B,
 #pragma unroll
         for (int k = 0; k < PH_MAXB / 64; ++k) a += rl[lane + 64 * k];
         a = ph_wave_sum(a);
-        if (n_rows == nullptr) {
+        if (!CRIT && n_rows == nullptr) {
             if (lane == 0) loss[0] = a / (float)B;
         } else {                                            // the mean over the rows that have a label: counted here, in floats (exact: B <= 1024)
             float c = 0.f;
@@ -257,26 +274,33 @@ __global__ __launch_bounds__(PH_FIN_WAVES * 64) void ph_fwd_finish_kernel(int B,
                 const int b = lane + 64 * k;
                 if (b < B) {
                     const long long label = labels[b];
-                    c += label >= 0 && label < NL ? 1.f : 0.f;
+                    if constexpr (CRIT)                     // the weighted mean's divisor: sum of w[label] over the labelled rows
+                        c += label >= 0 && label < NL ? (class_w != nullptr ? class_w[label] : 1.f) : 0.f;
+                    else
+                        c += label >= 0 && label < NL ? 1.f : 0.f;
                 }
             }
             c = ph_wave_sum(c);
             if (lane == 0) {
-                n_rows[0] = (int)c;                         // an ordinary vector store
+                if constexpr (CRIT)
+                    den[0] = c;
+                else
+                    n_rows[0] = (int)c;                     // an ordinary vector store
                 loss[0] = c > 0.f ? a / c : 0.f;
             }
         }
     }
 }
 
-template <typename T>
+template <typename T, bool CRIT>
 __global__ __launch_bounds__(PH_THREADS) void ph_bwd_token_kernel(int B, int L, int H, int NL, int chunk, int NS, const float* __restrict__ dloss,
                                                                   const T* __restrict__ h, const T* __restrict__ ph, const float* __restrict__ qq,
                                                                   const float* __restrict__ vw, const float* __restrict__ W, const long long* __restrict__ labels,
                                                                   const float* __restrict__ logits, const float* __restrict__ alpha,
                                                                   const float* __restrict__ pooled, const float* __restrict__ keep, T* __restrict__ dh,
                                                                   T* __restrict__ dph, float* __restrict__ pq, float* __restrict__ pv, float* __restrict__ pvb,
-                                                                  float* __restrict__ dlg, const int* __restrict__ n_rows) {
+                                                                  float* __restrict__ dlg, const int* __restrict__ n_rows, const float* __restrict__ class_w,
+                                                                  float eps, const float* __restrict__ den) {
     constexpr int VN = Vec<T>::N, JMAX = PH_MAXH / (VN * 64);
     __shared__ float sdp[PH_MAXH];
     __shared__ float sq[PH_WAVES][PH_MAXH], sv[PH_WAVES][PH_MAXH];
@@ -297,13 +321,35 @@ __global__ __launch_bounds__(PH_THREADS) void ph_bwd_token_kernel(int B, int L, 
         dl[n] = n < NL ? expf(dl[n] - mx) : 0.f;
         z += dl[n];
     }
-    const int nr = n_rows == nullptr ? B : n_rows[0];
-    const float g = nr > 0 ? dloss[0] / (float)nr : 0.f;
+    float g;
+    if constexpr (CRIT) {
+        const float dn = den[0];
+        g = dn > 0.f ? dloss[0] / dn : 0.f;
+    } else {
+        const int nr = n_rows == nullptr ? B : n_rows[0];
+        g = nr > 0 ? dloss[0] / (float)nr : 0.f;
+    }
     const long long label = labels[b];
+    float k1 = 1.f, k2 = 0.f, tsum = 1.f, cw[PH_MAXNL];
+    if constexpr (CRIT) {                                   // include/fmmt_loss.h: t_n = (1 - eps) w[y] [n == y] + eps / NL w_n, d(logits) = g (p sum_n t_n - t)
+        float wy = 0.f, wsum = 0.f;
+#pragma unroll
+        for (int n = 0; n < PH_MAXNL; ++n) {
+            cw[n] = n < NL ? (class_w != nullptr ? class_w[n] : 1.f) : 0.f;
+            wy = n == (int)label ? cw[n] : wy;
+            wsum += cw[n];
+        }
+        k1 = (1.0f - eps) * wy;
+        k2 = eps / (float)NL;
+        tsum = fmaf(k2, wsum, k1);
+    }
 #pragma unroll
     for (int n = 0; n < PH_MAXNL; ++n) {
         const bool valid = label >= 0 && label < NL;
-        dl[n] = valid && n < NL ? g * (dl[n] / z - (n == (int)label ? 1.f : 0.f)) : 0.f;
+        if constexpr (CRIT)
+            dl[n] = valid && n < NL ? g * (dl[n] / z * tsum - fmaf(k2, cw[n], n == (int)label ? k1 : 0.f)) : 0.f;
+        else
+            dl[n] = valid && n < NL ? g * (dl[n] / z - (n == (int)label ? 1.f : 0.f)) : 0.f;
         if (s == 0 && tid == n) dlg[(size_t)b * PH_MAXNL + n] = dl[n];
     }
     // d(pooled) = keep * W^T d(logits), and its product with the pooled vector
@@ -462,10 +508,17 @@ extern "C" size_t fmmt_pool_head_bwd_workspace(int B, int L, int H) {
 
 namespace {
 
-// both forward entry points: n_rows == NULL divides by B, else by the counted rows (stored in n_rows[0])
+// the loss of include/fmmt_loss.h behind the classifier: den != NULL instantiates the finishing / token kernels with it
+struct PhCrit {
+    const float* class_w = nullptr;
+    float eps = 0.f;
+    float* den = nullptr;
+};
+
+// the forward entry points: n_rows == NULL divides by B, else by the counted rows (stored in n_rows[0]); crit.den: by the weight sum stored there
 int ph_fwd(int dtype, int B, int L, int H, int NL, const void* h, const void* ph, const float* qq, const float* value_w, const float* value_b, const float* mask,
            const float* cls_w, const float* cls_b, const int64_t* labels, float p, uint64_t seed, const uint64_t* seed_dev, float* logits, float* loss, float* alpha,
-           float* pooled, float* keep, int32_t* n_rows, void* workspace, size_t workspace_bytes, void* stream) {
+           float* pooled, float* keep, int32_t* n_rows, void* workspace, size_t workspace_bytes, void* stream, PhCrit crit = PhCrit()) {
     if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
     if (!(p >= 0.f) || !(p < 1.f)) return FMMT_EINVAL;
     if (!h || !ph || !qq || !value_w || !value_b || !mask || !cls_w || !cls_b || !labels || !logits || !loss || !alpha || !pooled || !keep || !workspace) return FMMT_EINVAL;
@@ -485,16 +538,22 @@ int ph_fwd(int dtype, int B, int L, int H, int NL, const void* h, const void* ph
                            alpha, ml, ppool);
     FMMT_CHECK_LAUNCH();
     const int nw = B < PH_FIN_WAVES ? B : PH_FIN_WAVES;
-    hipLaunchKernelGGL(ph_fwd_finish_kernel, dim3(1), dim3(nw * 64), 0, st, B, L, H, NL, NS, ml, ppool, cls_w, cls_b, (const long long*)labels, p,
-                       (unsigned long long)seed, (const unsigned long long*)seed_dev, alpha, pooled, keep, logits, loss, (int*)n_rows);
+    if (crit.den != nullptr)
+        hipLaunchKernelGGL(ph_fwd_finish_kernel<true>, dim3(1), dim3(nw * 64), 0, st, B, L, H, NL, NS, ml, ppool, cls_w, cls_b, (const long long*)labels, p,
+                           (unsigned long long)seed, (const unsigned long long*)seed_dev, alpha, pooled, keep, logits, loss, (int*)nullptr, crit.class_w, crit.eps,
+                           crit.den);
+    else
+        hipLaunchKernelGGL(ph_fwd_finish_kernel<false>, dim3(1), dim3(nw * 64), 0, st, B, L, H, NL, NS, ml, ppool, cls_w, cls_b, (const long long*)labels, p,
+                           (unsigned long long)seed, (const unsigned long long*)seed_dev, alpha, pooled, keep, logits, loss, (int*)n_rows, (const float*)nullptr, 0.f,
+                           (float*)nullptr);
     FMMT_CHECK_LAUNCH();
     return 0;
 }
 
-// both backward entry points: n_rows == NULL divides by B, else by the device word the forward wrote
+// the backward entry points: crit.den != NULL divides by that float device word; n_rows == NULL divides by B, else by the device word the forward wrote
 int ph_bwd(int dtype, int B, int L, int H, int NL, const float* dloss, const void* h, const void* ph, const float* qq, const float* value_w, const float* cls_w,
            const int64_t* labels, const float* logits, const float* alpha, const float* pooled, const float* keep, const int32_t* n_rows, void* dh, void* dph,
-           float* dqq, float* dv, float* dvb, float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+           float* dqq, float* dv, float* dvb, float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream, PhCrit crit = PhCrit()) {
     if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
     if (!dloss || !h || !ph || !qq || !value_w || !cls_w || !labels || !logits || !alpha || !pooled || !keep || !dh || !dph || !dqq || !dv || !dvb || !dW || !db ||
         !workspace)
@@ -511,12 +570,20 @@ int ph_bwd(int dtype, int B, int L, int H, int NL, const float* dloss, const voi
     float* dlg = (float*)(w + 2 * ph_round(np * H * 4) + ph_round(np * 4));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(NS, B);
-    if (dtype == FMMT_BF16)
-        hipLaunchKernelGGL(ph_bwd_token_kernel<bf16>, grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const bf16*)h, (const bf16*)ph, qq, value_w, cls_w,
-                           (const long long*)labels, logits, alpha, pooled, keep, (bf16*)dh, (bf16*)dph, pq, pv, pvb, dlg, (const int*)n_rows);
+    const float* cwp = crit.class_w;
+    const float* dnp = crit.den;
+    if (dtype == FMMT_BF16 && dnp != nullptr)
+        hipLaunchKernelGGL((ph_bwd_token_kernel<bf16, true>), grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const bf16*)h, (const bf16*)ph, qq, value_w,
+                           cls_w, (const long long*)labels, logits, alpha, pooled, keep, (bf16*)dh, (bf16*)dph, pq, pv, pvb, dlg, (const int*)nullptr, cwp, crit.eps, dnp);
+    else if (dtype == FMMT_BF16)
+        hipLaunchKernelGGL((ph_bwd_token_kernel<bf16, false>), grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const bf16*)h, (const bf16*)ph, qq, value_w,
+                           cls_w, (const long long*)labels, logits, alpha, pooled, keep, (bf16*)dh, (bf16*)dph, pq, pv, pvb, dlg, (const int*)n_rows, cwp, 0.f, dnp);
+    else if (dnp != nullptr)
+        hipLaunchKernelGGL((ph_bwd_token_kernel<float, true>), grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const float*)h, (const float*)ph, qq, value_w,
+                           cls_w, (const long long*)labels, logits, alpha, pooled, keep, (float*)dh, (float*)dph, pq, pv, pvb, dlg, (const int*)nullptr, cwp, crit.eps, dnp);
     else
-        hipLaunchKernelGGL(ph_bwd_token_kernel<float>, grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const float*)h, (const float*)ph, qq, value_w, cls_w,
-                           (const long long*)labels, logits, alpha, pooled, keep, (float*)dh, (float*)dph, pq, pv, pvb, dlg, (const int*)n_rows);
+        hipLaunchKernelGGL((ph_bwd_token_kernel<float, false>), grid, dim3(PH_THREADS), 0, st, B, L, H, NL, chunk, NS, dloss, (const float*)h, (const float*)ph, qq, value_w,
+                           cls_w, (const long long*)labels, logits, alpha, pooled, keep, (float*)dh, (float*)dph, pq, pv, pvb, dlg, (const int*)n_rows, cwp, 0.f, dnp);
     FMMT_CHECK_LAUNCH();
     hipLaunchKernelGGL(ph_bwd_finish_kernel, dim3((H + 63) / 64), dim3(64), 0, st, B, H, NL, NS, pq, pv, pvb, dlg, pooled, keep, dqq, dv, dvb, dW, db);
     FMMT_CHECK_LAUNCH();
@@ -560,4 +627,33 @@ extern "C" int fmmt_pool_head_bwd_rows(int dtype, int B, int L, int H, int NL, c
     if (!n_rows) return FMMT_EINVAL;
     return ph_bwd(dtype, B, L, H, NL, dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, n_rows, dh, dph, dqq, dv, dvb, dW, db, workspace,
                   workspace_bytes, stream);
+}
+
+// the head with the loss of include/fmmt_loss.h: the same launches, the divisor a float device word (sum of w[label] over the labelled rows)
+extern "C" int fmmt_pool_head_fwd_crit(int dtype, int B, int L, int H, int NL, const void* h, const void* ph, const float* qq, const float* value_w,
+                                       const float* value_b, const float* mask, const float* cls_w, const float* cls_b, const int64_t* labels, float p,
+                                       uint64_t seed, const uint64_t* seed_dev, float* logits, float* loss, float* alpha, float* pooled, float* keep,
+                                       const float* class_w, float smoothing, float* den, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
+    if (!den || !(smoothing >= 0.f) || !(smoothing < 1.f)) return FMMT_EINVAL;
+    PhCrit crit;
+    crit.class_w = class_w;
+    crit.eps = smoothing;
+    crit.den = den;
+    return ph_fwd(dtype, B, L, H, NL, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, seed_dev, logits, loss, alpha, pooled, keep, nullptr, workspace,
+                  workspace_bytes, stream, crit);
+}
+
+extern "C" int fmmt_pool_head_bwd_crit(int dtype, int B, int L, int H, int NL, const float* dloss, const void* h, const void* ph, const float* qq,
+                                       const float* value_w, const float* cls_w, const int64_t* labels, const float* logits, const float* alpha,
+                                       const float* pooled, const float* keep, const float* class_w, float smoothing, const float* den, void* dh, void* dph,
+                                       float* dqq, float* dv, float* dvb, float* dW, float* db, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = ph_check_shape(dtype, B, L, H, NL)) return rc;
+    if (!den || !(smoothing >= 0.f) || !(smoothing < 1.f)) return FMMT_EINVAL;
+    PhCrit crit;
+    crit.class_w = class_w;
+    crit.eps = smoothing;
+    crit.den = const_cast<float*>(den);
+    return ph_bwd(dtype, B, L, H, NL, dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, nullptr, dh, dph, dqq, dv, dvb, dW, db, workspace,
+                  workspace_bytes, stream, crit);
 }

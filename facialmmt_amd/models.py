@@ -339,13 +339,14 @@ class meld_utt_transformer(nn.Module):
         pooled, _ = self.attention(h, utt_mask)
         return self.classifier(self.mm_dropout(pooled))
 
-    def forward_loss(self, inputs=None, utt_mask=None, labels=None, valid_mean=False):
+    def forward_loss(self, inputs=None, utt_mask=None, labels=None, valid_mean=False, criterion=None):
         """(loss, logits) of a training / validation batch (train.py:256-258, :283-285: the model, then cross_entropy): the encoder as `forward` runs it,
         the pooling's two Linear layers (P over the tokens, Q over the query vector) on ops.linear, and everything behind them -- tanh, scores, masked
         softmax, weighted sum, dropout, classifier, cross-entropy -- as ops.pool_head_loss (two launches per direction).  eval(): no dropout.  The
         reference's pooling returns the squeezed input for a one-token sequence (modules/Transformer.py:26-27); a loss has no use for that: L == 1 raises.
         valid_mean: the loss is the mean over the rows whose label lies in [0, num_labels) -- a short batch padded with label -100 rows
-        (train_step.pad_unimodal_batch) then gives the compact batch's loss and gradients; every label valid: the same bits as without it."""
+        (train_step.pad_unimodal_batch) then gives the compact batch's loss and gradients; every label valid: the same bits as without it.
+        criterion (None: the plain cross-entropy; else a train_step.Criterion): the class-weighted, label-smoothed mean over the labelled rows."""
         from . import ops
         if inputs.shape[1] == 1:
             raise ValueError("meld_utt_transformer.forward_loss: a sequence of one token has no attention pooling to train")
@@ -359,4 +360,4 @@ class meld_utt_transformer(nn.Module):
         qq = ops.linear(att.query_vector.to(cd).unsqueeze(0), att.Q.weight, att.Q.bias).float().reshape(-1)
         p = self.mm_dropout.p if self.training else 0.0
         seed = ops.draw_seed(h.device) if p > 0 else 0
-        return ops.pool_head_loss(hc, ph, qq, att.value.weight, att.value.bias, utt_mask, self.classifier.weight, self.classifier.bias, labels, p, seed, valid_mean)
+        return ops.pool_head_loss(hc, ph, qq, att.value.weight, att.value.bias, utt_mask, self.classifier.weight, self.classifier.bias, labels, p, seed, valid_mean, criterion)

@@ -2277,17 +2277,77 @@ def pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, p
     return dh, dph, dqq, dv, dvb, dW, db
 
 
+def _criterion_args(who, criterion, NL, dev):
+    """(class weights or None, eps) of a criterion -- anything with `.weight` (None, or the fp32 (NL,) tensor on `dev` the launches address) and
+    `.label_smoothing`, train_step.Criterion being the one the steps hold"""
+    w, eps = criterion.weight, float(criterion.label_smoothing)
+    if not 0.0 <= eps < 1.0:
+        raise _lib.FmmtError(f"{who}: label_smoothing must lie in [0, 1), got {eps}")
+    if w is not None and (not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != (NL,) or not w.is_contiguous() or w.device != dev):
+        raise _lib.FmmtError(f"{who}: the class weights must be a contiguous fp32 ({NL},) tensor on {dev}")
+    return w, eps
+
+
+def pool_head_fwd_crit_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, weight, eps):
+    """fmmt_pool_head_fwd_crit on tensors (no autograd): pool_head_fwd_raw(..., valid_mean=True) with the class-weighted, label-smoothed loss of
+    include/fmmt_loss.h -- weight: None or fp32 (NL,) on the device, eps: float.  The sixth result is den (1,) fp32, the device word
+    pool_head_bwd_crit_raw takes."""
+    (B, L, H, NL), h2, ph2, (q, vw, vb, mk, cw, cb), lab = _pool_head_args(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels)
+    dev = h2.device
+    lib = _lib.load()
+    logits = torch.empty((B, NL), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    alpha = torch.empty((B, L), dtype=torch.float32, device=dev)
+    pooled, keep = torch.empty((B, H), dtype=torch.float32, device=dev), torch.empty((B, H), dtype=torch.float32, device=dev)
+    den = torch.empty((1,), dtype=torch.float32, device=dev)
+    nbytes = lib.fmmt_pool_head_bwd_workspace(B, L, H)
+    ws = _ws(nbytes, dev)
+    seed_i, seed_t = _seed_args(seed)
+    check(lib.fmmt_pool_head_fwd_crit(dtype_code(h2.dtype), B, L, H, NL, _p(h2), _p(ph2), _p(q), _p(vw), _p(vb), _p(mk), _p(cw), _p(cb), _p(lab), float(p),
+                                      seed_i, _p(seed_t), _p(logits), _p(loss), _p(alpha), _p(pooled), _p(keep), _p(weight), float(eps), _p(den), _p(ws), nbytes,
+                                      _st()), f"fmmt_pool_head_fwd_crit(B={B},L={L},H={H},NL={NL})")
+    return loss, logits, alpha, pooled, keep, den
+
+
+def pool_head_bwd_crit_raw(dloss, h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, weight, eps, den):
+    """fmmt_pool_head_bwd_crit on tensors: pool_head_bwd_raw's results under the criterion of the forward; den: the fp32 word it wrote"""
+    B, L, H = h.shape
+    NL = cls_w.shape[0]
+    dev = h.device
+    lib = _lib.load()
+    h2, ph2 = _c16(h.detach()), _c16(ph.detach())
+    q, vw, cw = (_c16(t.detach().reshape(-1).float()) for t in (qq, value_w, cls_w))
+    dl = dloss.detach().reshape(-1).float().contiguous()
+    if den.dtype != torch.float32 or den.device != dev or den.numel() < 1:
+        raise _lib.FmmtError(f"pool_head_loss: den must be the fp32 word of the forward on {dev}")
+    dh, dph = torch.empty_like(h2), torch.empty_like(h2)
+    dqq, dv = torch.empty((H,), dtype=torch.float32, device=dev), torch.empty((H,), dtype=torch.float32, device=dev)
+    dvb = torch.empty((1,), dtype=torch.float32, device=dev)
+    dW, db = torch.empty((NL, H), dtype=torch.float32, device=dev), torch.empty((NL,), dtype=torch.float32, device=dev)
+    nbytes = lib.fmmt_pool_head_bwd_workspace(B, L, H)
+    ws = _ws(nbytes, dev)
+    check(lib.fmmt_pool_head_bwd_crit(dtype_code(h2.dtype), B, L, H, NL, _p(dl), _p(h2), _p(ph2), _p(q), _p(vw), _p(cw), _p(labels), _p(logits), _p(alpha),
+                                      _p(pooled), _p(keep), _p(weight), float(eps), _p(den), _p(dh), _p(dph), _p(dqq), _p(dv), _p(dvb), _p(dW), _p(db), _p(ws),
+                                      nbytes, _st()), f"fmmt_pool_head_bwd_crit(B={B},L={L},H={H},NL={NL})")
+    return dh, dph, dqq, dv, dvb, dW, db
+
+
 class PoolHeadLossFn(Function):
     """(loss, logits) of the V-only classifier's tail behind ph = P h + b_P and qq = Q query_vector + b_Q (modules/Transformer.py:24-45, src/models.py:219-221,
     train.py:258): two launches forward, two backward (csrc/pool_head.hip).  The gradient flows from the loss; the logits are returned for the caller's
     bookkeeping and are not differentiable.  Saved: alpha, the pooled vector, the keep mask (the dropout is not replayed: B x H values).
-    valid_mean: the fmmt_pool_head_*_rows pair (mean over the labelled rows); the row count stays a device word in the context."""
+    valid_mean: the fmmt_pool_head_*_rows pair (mean over the labelled rows); the row count stays a device word in the context.
+    criterion ((class weights or None, eps), of _criterion_args): the fmmt_pool_head_*_crit pair -- the weighted mean over the labelled rows, its
+    divisor a float device word in the context; valid_mean is then implied."""
 
     @staticmethod
-    def forward(ctx, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, valid_mean=False):
+    def forward(ctx, h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, valid_mean=False, criterion=None):
         _need_cuda(h, "pool_head_loss")
         lab = labels.detach().to(device=h.device, dtype=torch.int64).contiguous()      # once: the raw call below finds it as it needs it
-        if valid_mean:
+        ctx.crit = criterion
+        if criterion is not None:
+            loss, logits, alpha, pooled, keep, ctx.n_rows = pool_head_fwd_crit_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed, *criterion)
+        elif valid_mean:
             loss, logits, alpha, pooled, keep, ctx.n_rows = pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed, True)
         else:
             loss, logits, alpha, pooled, keep = pool_head_fwd_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, lab, p, seed)
@@ -2301,13 +2361,91 @@ class PoolHeadLossFn(Function):
     @staticmethod
     def backward(ctx, dloss, _dlogits):
         h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep = ctx.saved_tensors
-        dh, dph, dqq, dv, dvb, dW, db = pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep, ctx.n_rows)
+        if ctx.crit is not None:
+            dh, dph, dqq, dv, dvb, dW, db = pool_head_bwd_crit_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep, *ctx.crit, ctx.n_rows)
+        else:
+            dh, dph, dqq, dv, dvb, dW, db = pool_head_bwd_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep, ctx.n_rows)
         sh, dt = ctx.shapes, ctx.dtypes
         outs = [g.reshape(s).to(d) for g, s, d in zip((dqq, dv, dvb, dW, db), sh, dt)]
-        return dh.reshape(h.shape), dph.reshape(h.shape), outs[0], outs[1], outs[2], None, outs[3], outs[4], None, None, None, None
+        return dh.reshape(h.shape), dph.reshape(h.shape), outs[0], outs[1], outs[2], None, outs[3], outs[4], None, None, None, None, None
 
 
-def pool_head_loss(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0, valid_mean=False):
+def pool_head_loss(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p=0.0, seed=0, valid_mean=False, criterion=None):
     """-> (loss, logits): mean cross-entropy of classifier(dropout(additive-attention pooling of h)) and the logits (see PoolHeadLossFn).  valid_mean:
-    the mean runs over the rows whose label lies in [0, NL) (F.cross_entropy's ignore_index rule for a padded batch) instead of over all B rows."""
-    return PoolHeadLossFn.apply(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, bool(valid_mean))
+    the mean runs over the rows whose label lies in [0, NL) (F.cross_entropy's ignore_index rule for a padded batch) instead of over all B rows.
+    criterion (None: the launches above; else an object with `.weight` and `.label_smoothing`, train_step.Criterion): the class-weighted,
+    label-smoothed mean of include/fmmt_loss.h over the labelled rows (fmmt_pool_head_fwd_crit / _bwd_crit)."""
+    if criterion is None:
+        return PoolHeadLossFn.apply(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, bool(valid_mean))
+    crit = _criterion_args("pool_head_loss", criterion, cls_w.shape[0], h.device)
+    return PoolHeadLossFn.apply(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, True, crit)
+
+
+# ------------------------------------------------------------------------------------------------
+# class-weighted, label-smoothed cross-entropy of (B, NL) logits (csrc/ce_loss.hip, include/fmmt_loss.h)
+# ------------------------------------------------------------------------------------------------
+def _ce_args(logits, labels, weight):
+    _need_cuda(logits, "ce_loss")
+    if logits.dim() != 2 or tuple(labels.shape) != (logits.shape[0],):
+        raise _lib.FmmtError(f"ce_loss: logits (B, NL) and labels (B,) expected, got {tuple(logits.shape)} / {tuple(labels.shape)}")
+    B, NL = logits.shape
+    if not 1 <= NL <= _lib.CE_MAXNL or not 1 <= B <= _lib.CE_MAXB:
+        raise _lib.FmmtError(f"ce_loss: 1 <= NL <= {_lib.CE_MAXNL} classes and 1 <= B <= {_lib.CE_MAXB} rows, got B={B}, NL={NL}")
+    lg = logits.detach()
+    if lg.stride(1) != 1 or lg.stride(0) < NL:
+        lg = lg.contiguous()
+    dev = lg.device
+    if weight is not None and (not torch.is_tensor(weight) or weight.dtype != torch.float32 or tuple(weight.shape) != (NL,) or not weight.is_contiguous()
+                               or weight.device != dev):
+        raise _lib.FmmtError(f"ce_loss: the class weights must be a contiguous fp32 ({NL},) tensor on {dev}")
+    lab = labels.detach().to(device=dev, dtype=torch.int64).contiguous()
+    return B, NL, lg, lab
+
+
+def ce_fwd_raw(logits, labels, weight=None, label_smoothing=0.0):
+    """fmmt_ce_fwd on tensors (no autograd): logits (B, NL) bf16 / fp32 (rows may be a strided view, stride(0) >= NL), labels (B,) (a label outside
+    [0, NL) is ignored), weight None or fp32 (NL,) on the device.  Returns (loss (), den (1,)), fp32 device words; one launch, no host read."""
+    B, NL, lg, lab = _ce_args(logits, labels, weight)
+    loss = torch.empty((), dtype=torch.float32, device=lg.device)
+    den = torch.empty((1,), dtype=torch.float32, device=lg.device)
+    check(_lib.load().fmmt_ce_fwd(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), _p(weight), float(label_smoothing), _p(loss), _p(den), _st()),
+          f"fmmt_ce_fwd(B={B},NL={NL})")
+    return loss, den
+
+
+def ce_bwd_raw(dloss, logits, labels, weight, label_smoothing, den):
+    """fmmt_ce_bwd on tensors: d(logits) (B, NL), contiguous, in the logits' dtype; dloss and den (the word ce_fwd_raw wrote) are read on the device"""
+    B, NL, lg, lab = _ce_args(logits, labels, weight)
+    dev = lg.device
+    if den.dtype != torch.float32 or den.device != dev or den.numel() < 1:
+        raise _lib.FmmtError(f"ce_loss: den must be the fp32 word of the forward on {dev}")
+    dl = dloss.detach().reshape(-1).float().contiguous()
+    out = torch.empty((B, NL), dtype=lg.dtype, device=dev)
+    check(_lib.load().fmmt_ce_bwd(dtype_code(lg.dtype), B, NL, _p(lg), lg.stride(0), _p(lab), _p(weight), float(label_smoothing), _p(dl), _p(den), _p(out), NL,
+                                  _st()), f"fmmt_ce_bwd(B={B},NL={NL})")
+    return out
+
+
+class CeLossFn(Function):
+    """torch.nn.CrossEntropyLoss(weight, label_smoothing, reduction='mean') of (B, NL) logits (train.py:26,135 with the criterion a run chose), one
+    launch forward and one backward (csrc/ce_loss.hip); den == 0 gives loss 0 and a zero gradient (include/fmmt_loss.h).  The weights are read on
+    the device at launch time: a captured graph follows a weight tensor changed in place."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, label_smoothing):
+        loss, den = ce_fwd_raw(logits, labels, weight, label_smoothing)
+        ctx.save_for_backward(logits, labels, den)
+        ctx.weight, ctx.eps = weight, float(label_smoothing)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, labels, den = ctx.saved_tensors
+        return ce_bwd_raw(dloss, logits, labels, ctx.weight, ctx.eps, den), None, None, None
+
+
+def ce_loss(logits, labels, weight=None, label_smoothing=0.0):
+    """-> loss (): the class-weighted, label-smoothed mean cross-entropy of (B, NL) bf16 / fp32 logits (see CeLossFn)"""
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise _lib.FmmtError(f"ce_loss: label_smoothing must lie in [0, 1), got {label_smoothing}")
+    return CeLossFn.apply(logits, labels, weight, float(label_smoothing))

@@ -26,6 +26,9 @@ Registered (forward ops return what their backward needs as extra outputs, as cu
     fmmt::eval_accumulate_at(logits, labels, acc!, cursor!, logits_out!, labels_out!, pred_out!?) -> ()   the same update, the batch's rows kept at a device-held row index that it advances
     fmmt::eval_accumulate_rows(logits, labels, acc!, cursor!, n_rows, logits_out!, labels_out!, pred_out!?) -> ()   that update for a padded batch: a device word says how many rows exist
     fmmt::eval_merge(words, results, truths, words_out!, results_out!, truths_out!) -> ()   W gathered shards of a split (accumulators, cursors, rows) -> the split in rank order
+    fmmt::ce_loss(logits, labels, weight?, label_smoothing) -> (loss, den)                 class-weighted, label-smoothed mean cross-entropy of (B, NL) logits, one launch per direction
+    fmmt::pool_head_loss_crit(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, weight?, label_smoothing)
+                       -> (loss, logits, alpha, pooled, keep, den)                         the V-only classifier's tail behind its two GEMMs with that loss (two launches per direction)
 
 The nn.Modules of facialmmt_amd/modules keep using ops.py (fewer dispatcher hops per launch); tests/test_gpu_torch_ops.py
 holds the two front ends bit-identical, forward and backward, and runs torch.library.opcheck on each operator."""
@@ -487,3 +490,60 @@ def eval_merge(words: Tensor, results: Tensor, truths: Tensor, words_out: Tensor
 @eval_merge.register_fake
 def _(words, results, truths, words_out, results_out, truths_out):
     return None
+
+
+# ------------------------------------------------------------------------------------------------ the training loss (include/fmmt_loss.h)
+@torch.library.custom_op(f"{_LIB}::ce_loss", mutates_args=(), device_types="cuda")
+def ce_loss(logits: Tensor, labels: Tensor, weight: Optional[Tensor], label_smoothing: float) -> Tuple[Tensor, Tensor]:
+    return ops.ce_fwd_raw(logits, labels, weight, label_smoothing)
+
+
+@ce_loss.register_fake
+def _(logits, labels, weight, label_smoothing):
+    return logits.new_empty((), dtype=torch.float32), logits.new_empty((1,), dtype=torch.float32)
+
+
+def _ce_setup(ctx, inputs, output):
+    logits, labels, weight, eps = inputs
+    ctx.save_for_backward(logits, labels, weight, output[1])
+    ctx.eps = eps
+
+
+def _ce_backward(ctx, dloss, _dden):
+    logits, labels, weight, den = ctx.saved_tensors
+    return ops.ce_bwd_raw(dloss, logits, labels, weight, ctx.eps, den), None, None, None
+
+
+ce_loss.register_autograd(_ce_backward, setup_context=_ce_setup)
+
+
+@torch.library.custom_op(f"{_LIB}::pool_head_loss_crit", mutates_args=(), device_types="cuda")
+def pool_head_loss_crit(h: Tensor, ph: Tensor, qq: Tensor, value_w: Tensor, value_b: Tensor, mask: Tensor, cls_w: Tensor, cls_b: Tensor, labels: Tensor,
+                        p: float, seed: int, weight: Optional[Tensor], label_smoothing: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    return ops.pool_head_fwd_crit_raw(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, weight, label_smoothing)
+
+
+@pool_head_loss_crit.register_fake
+def _(h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, weight, label_smoothing):
+    B, L, H = h.shape
+    f = lambda *shape: h.new_empty(shape, dtype=torch.float32)
+    return f(), f(B, cls_w.shape[0]), f(B, L), f(B, H), f(B, H), f(1)
+
+
+def _phc_setup(ctx, inputs, output):
+    h, ph, qq, value_w, value_b, mask, cls_w, cls_b, labels, p, seed, weight, eps = inputs
+    _loss, logits, alpha, pooled, keep, den = output
+    ctx.save_for_backward(h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, weight, den)
+    ctx.eps = eps
+    ctx.like = (qq, value_w, value_b, cls_w, cls_b)
+
+
+def _phc_backward(ctx, dloss, *_unused):
+    h, ph, qq, value_w, cls_w, labels, logits, alpha, pooled, keep, weight, den = ctx.saved_tensors
+    lab = labels.to(device=h.device, dtype=torch.int64).contiguous()
+    dh, dph, dqq, dv, dvb, dW, db = ops.pool_head_bwd_crit_raw(dloss, h, ph, qq, value_w, cls_w, lab, logits, alpha, pooled, keep, weight, ctx.eps, den)
+    outs = [g.reshape(t.shape).to(t.dtype) for g, t in zip((dqq, dv, dvb, dW, db), ctx.like)]
+    return dh.reshape(h.shape), dph.reshape(h.shape), outs[0], outs[1], outs[2], None, outs[3], outs[4], None, None, None, None, None
+
+
+pool_head_loss_crit.register_autograd(_phc_backward, setup_context=_phc_setup)

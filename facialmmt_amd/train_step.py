@@ -298,6 +298,96 @@ def row_weight(b, world, global_rows, captured_rows=None):
     return b * world / g
 
 
+class Criterion:
+    """The loss a run chooses, torch.nn.CrossEntropyLoss(weight=w, label_smoothing=eps, reduction='mean') -- the value the reference sets once and
+    hands every loop (train.py:295 -> :26,135,256) -- as a construction argument of the six training steps (CRITERION_NOTE at GraphedTargetStep.__init__).
+    `weight` (None: every class counts 1): NL finite numbers >= 0, kept as ONE fp32 tensor on `device` (default: the current GPU, the CPU without
+    one) that every captured launch addresses: `step.criterion.weight.copy_(new)` between steps is seen by the next replay, nothing is rebound.
+    `label_smoothing`: eps in [0, 1), a host float the launches carry.  ValueError for anything else.
+    Calling it, criterion(logits, labels) with logits (B, NL) and labels (B,) (a label outside [0, NL) is ignored: -100, a padded row), gives the
+    mean loss: on the GPU ops.ce_loss (csrc/ce_loss.hip, one launch per direction, bf16 / fp32 logits read as they are), on the CPU `reference`.
+    DEPARTURE from torch (include/fmmt_loss.h): a batch whose labelled rows weigh 0 together gives loss 0 and a zero gradient, not NaN.
+    Not part of any state_dict(): like the betas it is given again when a run is resumed."""
+
+    def __init__(self, weight=None, label_smoothing=0.0, device=None):
+        eps = float(label_smoothing)
+        if not 0.0 <= eps < 1.0:                             # NaN fails both comparisons
+            raise ValueError(f"Criterion: label_smoothing must lie in [0, 1), got {label_smoothing}")
+        self.label_smoothing = eps
+        if device is None:
+            device = weight.device if torch.is_tensor(weight) and weight.is_cuda else ("cuda" if torch.cuda.is_available() else "cpu")
+        self.weight = None
+        if weight is not None:
+            w = torch.as_tensor(weight).detach().to(dtype=torch.float32)
+            if w.dim() != 1 or not 1 <= w.numel() <= 8:
+                raise ValueError(f"Criterion: weight must hold one number per class, 1 <= NL <= 8, got shape {tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise ValueError("Criterion: the class weights must be finite and >= 0")
+            self.weight = w.to(device).contiguous().clone()
+
+    @property
+    def num_labels(self):
+        """NL the weights were given for; None without weights (any NL)"""
+        return None if self.weight is None else self.weight.numel()
+
+    def check_labels(self, num_labels):
+        """ValueError unless the weights, when there are any, count `num_labels` classes"""
+        if self.weight is not None and self.weight.numel() != int(num_labels):
+            raise ValueError(f"Criterion: {self.weight.numel()} class weights for {int(num_labels)} classes")
+
+    def __call__(self, logits, labels):
+        if not logits.is_cuda:
+            return self.reference(logits, labels)
+        from . import ops
+        self.check_labels(logits.shape[-1])
+        lg = logits if logits.dtype in (torch.float32, torch.bfloat16) else logits.float()
+        return ops.ce_loss(lg, labels, self.weight, self.label_smoothing)
+
+    def reference(self, logits, labels):
+        """The pure-torch statement of the formulas of include/fmmt_loss.h, in the dtype and on the device of `logits` (fp64 logits: the fp64
+        reference the tests hold the kernels to), differentiable by autograd.  den == 0: loss 0, gradient 0."""
+        x = logits
+        NL = x.shape[-1]
+        self.check_labels(NL)
+        eps = self.label_smoothing
+        lab = torch.as_tensor(labels).to(device=x.device, dtype=torch.int64)
+        valid = (lab >= 0) & (lab < NL)
+        y = lab.clamp(0, NL - 1)
+        w = torch.ones(NL, dtype=x.dtype, device=x.device) if self.weight is None else self.weight.to(device=x.device, dtype=x.dtype)
+        onehot = F.one_hot(y, NL).to(x.dtype)
+        t = valid.to(x.dtype).unsqueeze(1) * ((1.0 - eps) * w[y].unsqueeze(1) * onehot + (eps / NL) * w.unsqueeze(0))
+        num = -(t * torch.log_softmax(x, dim=-1)).sum()
+        den = (valid.to(x.dtype) * w[y]).sum()
+        some = den > 0
+        return torch.where(some, num / torch.where(some, den, torch.ones_like(den)), torch.zeros_like(num))
+
+
+def _check_criterion(criterion, num_labels=None):
+    """the steps' `criterion` argument: None (F.cross_entropy and the plain head, every launch as before) or a Criterion"""
+    if criterion is not None and not isinstance(criterion, Criterion):
+        raise ValueError("criterion: None (plain cross-entropy) or a train_step.Criterion")
+    if criterion is not None and num_labels is not None:
+        criterion.check_labels(num_labels)
+    return criterion
+
+
+def _loss_of(criterion, logits, labels):
+    """the mean loss of a step's (B, NL) logits: F.cross_entropy over the fp32 logits without a criterion -- the launches of before --, else the
+    criterion's one launch (the logits are read in their own dtype, which is what the cast in front of F.cross_entropy computes)"""
+    if criterion is None:
+        return F.cross_entropy(logits.float(), labels)
+    return criterion(logits, labels)
+
+
+def check_criterion_rows(who, criterion, global_rows):
+    """CRITERION_NOTE (at GraphedTargetStep.__init__), several ranks.  The ranks' weighted means are averaged by the exchange, which is what DDP over
+    nn.CrossEntropyLoss(weight=...) gives.  `global_rows` corrects the mean of means to the mean over all real rows by the ROW count; under class
+    weights the exact correction needs every rank's den (sum of w[label]), which the sampler does not know: ValueError.  With smoothing alone den
+    IS the row count and global_rows works as without a criterion.  Pure host code."""
+    if global_rows is not None and criterion is not None and criterion.weight is not None:
+        raise ValueError(f"{who}: global_rows together with class weights: the correction needs the ranks' weight sums, which no row count gives")
+
+
 def _check_global_rows(who, global_rows, weight_word, b, world, captured_rows):
     """the graphed steps' __call__: the weight this micro-step's loss is differentiated with (row_weight), or ValueError -- before any copy or launch"""
     if global_rows is not None and weight_word is None:
@@ -415,8 +505,9 @@ class TargetStep(StepState):
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "target", ("swin", "mm"), "trg_accumulation_steps"
 
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, autocast_dtype=None, ddp_model=None, averager=None,
-                 discarded_swin_gradients="compute", frame_capacity=None, color_jitter=None, token_capacity=None):
-        """Data parallel: pass `averager` (parallel.GradientAverager over the multimodal parameters) or, alternatively,
+                 discarded_swin_gradients="compute", frame_capacity=None, color_jitter=None, token_capacity=None, criterion=None):
+        """`criterion` (None: F.cross_entropy, the launches of before): a Criterion -- CRITERION_NOTE at GraphedTargetStep.
+        Data parallel: pass `averager` (parallel.GradientAverager over the multimodal parameters) or, alternatively,
         `ddp_model` (the module wrapped by torch's DistributedDataParallel).
         `color_jitter` (an augment.ColorJitter; None: no augmentation): the MELD train transform (utils/dataset.py:35-39,62-63) on the uint8 frames,
         inside the pre-step -- every call draws a table from the device generator for the frames Swin runs on and keeps it in `last_jitter`.
@@ -430,6 +521,7 @@ class TargetStep(StepState):
         its own batch's count rounded up to TOKEN_GRANULE (nothing here has a captured shape); an integer: that many rows, more real tokens raise
         ValueError; 0: the padded layout.  A mask with a hole takes the padded layout.  `token_rows`: what the last call ran with (0: padded).
         Not under `ddp_model` (torch's DDP calls the module through its own forward: the padded layout)."""
+        self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
         self.token_capacity = None if token_capacity is None else int(token_capacity)
         if self.token_capacity is not None and self.token_capacity < 0:
             raise ValueError("token_capacity: a number of rows, 0 (padded layout) or None (per batch)")
@@ -534,7 +626,7 @@ class TargetStep(StepState):
                 else:
                     logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
             mark("multimodal_fwd")
-            loss = F.cross_entropy(logits.float(), labels) / args.trg_accumulation_steps
+            loss = _loss_of(self.criterion, logits, labels) / args.trg_accumulation_steps
             loss.backward()
         mark("backward")
         if last:
@@ -1734,8 +1826,16 @@ class GraphedTargetStep(StepState):
     def __init__(self, swin_model, multimodal_model, optimizer, scheduler, args, batch, autocast_dtype=None,
                  overlap_text=True, parallel_fusion=False, averager=None, warmup_iters=2, masters=None, discarded_swin_gradients="compute",
                  swin_cut: int = 0, pipeline_swin: bool = False, branch_graphs: bool = False, fork_streams: bool = False, frame_capacity=None,
-                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None, grad_report: bool = False, token_capacity=None):
-        """`averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
+                 pad_rows: bool = False, skip_nonfinite: bool = False, color_jitter=None, grad_report: bool = False, token_capacity=None,
+                 criterion=None):
+        """`criterion` (None: F.cross_entropy, every launch as before): a Criterion.  CRITERION_NOTE: the loss a run chooses -- class weights, label
+        smoothing -- is a construction argument of all six training steps like the optimizer's betas.  A graphed step captures ops.ce_loss in the
+        place of F.cross_entropy (one launch per direction; GraphedUnimodalStep: the pooling head's _crit pair) in EVERY capture it makes (single
+        graph, branch_graphs, every capacity, the padded twin); the launches address `criterion.weight`, so weights copied into that tensor between
+        calls hold from the next replay on.  Padded rows (label -100) drop out of numerator and denominator; accumulation, skip_nonfinite, grad_report,
+        parameter groups, augmentation and resuming are untouched, and the criterion is in no state_dict().  Several ranks: the ranks' weighted means
+        are averaged; `global_rows` with class weights is a ValueError (check_criterion_rows).  Evaluation keeps the plain cross-entropy.
+        `averager`: GradientAverager(hooks=False) over the parameters the optimizer steps (default: the multimodal
         model's); `swin_cut`: with an exchange to hide (N > 1), the Swin stage behind which the backward graph is cut (0: the second
         piece is stage 0's backward, ~10 ms; 1: stages 1 + 0, ~17 ms) -- the caller picks it from a MEASURED exchange time
         (`pick_swin_cut`, bench.py), never from a nominal link rate; `masters`: optional MasterWeights of the text encoder -- then `averager` and the optimizer must have been
@@ -1814,6 +1914,7 @@ class GraphedTargetStep(StepState):
         self.twin_capture_bytes, self.twin_capture_reserved_bytes = {}, {}
         self._rows_now = self.token_capacity                # what the pass in progress (warm-up, capture) runs the text branch with: _text_rows sets it on
                                                             # the model for the length of that forward only, so nobody else who calls the model ever packs
+        self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
         self.skip_swin_bwd = discarded_swin_gradients == "skip"
         self.pipeline = bool(pipeline_swin)
         self.branches = bool(branch_graphs)                 # BRANCH_NOTE below
@@ -2146,7 +2247,7 @@ class GraphedTargetStep(StepState):
         vis_concat, new_mask = select_frames(preds_d.float(), vision_inputs, vision_mask, num_imgs, self.args.FacialEmoImpor_threshold)
         with ac():
             logits = self.mm.fusion_branch(feat_d, tmask, audio, audio_mask, vis_concat, new_mask)
-        loss = F.cross_entropy(logits.float(), labels) / self.args.trg_accumulation_steps
+        loss = _loss_of(self.criterion, logits, labels) / self.args.trg_accumulation_steps
         leaves = [l for l, _ in self.pairs if l.requires_grad]
         got = torch.autograd.grad(loss, [feat_d, preds_d] + leaves, allow_unused=True)
         for l, gr in zip(leaves, got[2:]):
@@ -2308,7 +2409,7 @@ class GraphedTargetStep(StepState):
                 for t in pending:
                     t.record_stream(main)
             logits = mm.fusion_branch(pending[0], pending[1], audio, audio_mask, vis_concat, new_mask)
-        loss = F.cross_entropy(logits.float(), labels) / args.trg_accumulation_steps
+        loss = _loss_of(self.criterion, logits, labels) / args.trg_accumulation_steps
         returned, w = loss, self.row_weight
         if w is not None:                                    # ROW_WEIGHT_NOTE: the gradients carry the weight, the loss handed back does not
             loss = loss * w
@@ -2409,6 +2510,7 @@ class GraphedTargetStep(StepState):
         `frame_counts`, `rows` and `padded_calls` are this rank's.  Not covered: a rank with no real row at all (b == 0 is refused)."""
         if len(batch) != len(self.static):
             raise ValueError(f"GraphedTargetStep: batch of {len(batch)} entries, captured with {len(self.static)}")
+        check_criterion_rows("GraphedTargetStep", self.criterion, global_rows)
         if global_rows is not None and (self.pipeline or self.branches):
             raise ValueError("GraphedTargetStep: global_rows needs pad_rows=True and an active gradient exchange")
         if self.pipeline:
@@ -2548,8 +2650,9 @@ class GraphedAuxStep(StepState):
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "aux", ("swin",), "aux_accumulation_steps"
 
     def __init__(self, swin_model, optimizer, scheduler, args, images, labels, averager=None, warmup_iters=2, pad_rows: bool = False,
-                 skip_nonfinite: bool = False, augment=None, grad_report: bool = False):
-        """`pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
+                 skip_nonfinite: bool = False, augment=None, grad_report: bool = False, criterion=None):
+        """`criterion` (None: F.cross_entropy, every launch as before): a Criterion -- CRITERION_NOTE at GraphedTargetStep.
+        `pad_rows` (default False: a batch of another shape raises ValueError): a batch with 1 <= b <= B images is padded to the captured B by
         pad_aux_batch (zero images, label -100) and replayed through the same graphs.  The capture then runs Swin with n_valid = a static int32
         device word that __call__ fills with b: the head's BatchNorm takes its statistics over the real rows only and a full batch
         (n_valid == B) gives the unmasked bits.  `rows`: the real rows of the last call; `padded_calls`: the calls that padded.
@@ -2565,6 +2668,7 @@ class GraphedAuxStep(StepState):
         from . import ops
         from .parallel import GradientAverager
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
+        self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
         self.augment, self.last_augment = _check_augment(augment), None
         if self.augment is not None:
             _need_u8_images(images)
@@ -2608,10 +2712,11 @@ class GraphedAuxStep(StepState):
         if self.augment is not None:                         # one record per image of the captured batch, drawn just ahead of Swin
             self.last_augment.copy_(self.augment.draw(images.shape[0], images.device))
             kw["augment"] = self.last_augment
+        crit = F.cross_entropy if self.criterion is None else self.criterion
         if self.pad_rows:
-            loss = self.swin(images, False, labels, F.cross_entropy, n_valid=self.n_valid, **kw) / self.args.aux_accumulation_steps
+            loss = self.swin(images, False, labels, crit, n_valid=self.n_valid, **kw) / self.args.aux_accumulation_steps
         else:
-            loss = self.swin(images, False, labels, F.cross_entropy, **kw) / self.args.aux_accumulation_steps
+            loss = self.swin(images, False, labels, crit, **kw) / self.args.aux_accumulation_steps
         (loss if self.row_weight is None else loss * self.row_weight).backward()
         self.tail.hand_over()
         if self.monitor is not None:
@@ -2622,6 +2727,7 @@ class GraphedAuxStep(StepState):
         """`global_rows`: GraphedTargetStep.__call__'s -- the real rows all ranks hold in this micro-step; pad_rows under an active exchange only"""
         if self.augment is not None:
             _need_u8_images(images)                          # ValueError before anything is copied or launched
+        check_criterion_rows("GraphedAuxStep", self.criterion, global_rows)
         rows = b = self.static[0].shape[0]
         padding = self.pad_rows and images.dim() == self.static[0].dim() and images.shape[0] != rows
         if padding:
@@ -2656,19 +2762,21 @@ class AuxStep(StepState):
     `aux_accumulation_steps`.  BASELINE.json configs[4] alternates these steps with target steps per epoch."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = GraphedAuxStep.STATE_KIND, GraphedAuxStep.STATE_MODELS, GraphedAuxStep.STATE_WINDOW
 
-    def __init__(self, swin_model, optimizer, scheduler, args, augment=None):
-        """`augment` (an augment.AffWildAugment; None: no augmentation): the Aff-Wild2 train transform (utils/util.py:22-60) on the uint8 images,
+    def __init__(self, swin_model, optimizer, scheduler, args, augment=None, criterion=None):
+        """`criterion` (None: F.cross_entropy): a Criterion -- CRITERION_NOTE at GraphedTargetStep.
+        `augment` (an augment.AffWildAugment; None: no augmentation): the Aff-Wild2 train transform (utils/util.py:22-60) on the uint8 images,
         inside the pre-step -- every call draws a table from the device generator, one record per image, and keeps it in `last_augment`."""
         self.swin, self.opt, self.sched, self.args = swin_model, optimizer, scheduler, args
         self.i_batch = 0
         self.augment, self.last_augment = _check_augment(augment), None
+        self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
 
     def __call__(self, images, labels):
         kw = {}
         if self.augment is not None:
             _need_u8_images(images)                          # ValueError before anything is launched
             self.last_augment = kw["augment"] = self.augment.draw(images.shape[0], images.device)
-        loss = self.swin(images, False, labels, F.cross_entropy, **kw) / self.args.aux_accumulation_steps
+        loss = self.swin(images, False, labels, F.cross_entropy if self.criterion is None else self.criterion, **kw) / self.args.aux_accumulation_steps
         loss.backward()
         self.i_batch += 1
         if self.i_batch % self.args.aux_accumulation_steps == 0:
@@ -2687,13 +2795,16 @@ class UnimodalStep(StepState):
     encoder -- pooling, dropout, classifier, loss -- is models.meld_utt_transformer.forward_loss (ops.pool_head_loss)."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = "unimodal", ("model",), "trg_accumulation_steps"
 
-    def __init__(self, model, optimizer, scheduler, args):
+    def __init__(self, model, optimizer, scheduler, args, criterion=None):
+        """`criterion` (None: the plain cross-entropy of the pooling head): a Criterion -- CRITERION_NOTE at GraphedTargetStep"""
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
+        self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
         self.i_batch = 0
 
     def __call__(self, batch):
         feature, mask, labels = batch
-        loss, _ = self.model.forward_loss(feature, mask, labels)
+        kw = {} if self.criterion is None else {"criterion": self.criterion}
+        loss, _ = self.model.forward_loss(feature, mask, labels, **kw)
         loss = loss / self.args.trg_accumulation_steps
         loss.backward()
         self.i_batch += 1
@@ -2727,13 +2838,16 @@ class GraphedUnimodalStep(StepState):
     `grad_report`: REPORT_NOTE -- `step.grad_report`, a GradReport named by model.named_parameters().
     `averager` (default None: this step never exchanges): a GradientAverager(hooks=False) over the model's parameters -- its buckets are averaged
     over the ranks between graph A and graph B of a window's last micro-step, as GraphedAuxStep does it; with pad_rows the call then takes
-    `global_rows` (ROW_WEIGHT_NOTE at GraphedTargetStep)."""
+    `global_rows` (ROW_WEIGHT_NOTE at GraphedTargetStep).
+    `criterion` (None: the plain or _rows head, every launch as before): a Criterion -- CRITERION_NOTE at GraphedTargetStep; the capture then runs
+    the pooling head's _crit pair, whose mean runs over the labelled rows with or without pad_rows."""
     STATE_KIND, STATE_MODELS, STATE_WINDOW = UnimodalStep.STATE_KIND, UnimodalStep.STATE_MODELS, UnimodalStep.STATE_WINDOW
 
     def __init__(self, model, optimizer, scheduler, args, batch, autocast_dtype=None, warmup_iters=2, pad_rows: bool = False,
-                 skip_nonfinite: bool = False, averager=None, grad_report: bool = False):
+                 skip_nonfinite: bool = False, averager=None, grad_report: bool = False, criterion=None):
         from . import ops
         self.model, self.opt, self.sched, self.args = model, optimizer, scheduler, args
+        self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
         self.autocast_dtype = autocast_dtype
         feature, mask, labels = batch
         self.static = [feature.clone(), mask.clone(), torch.as_tensor(labels, device=feature.device).clone()]
@@ -2773,6 +2887,8 @@ class GraphedUnimodalStep(StepState):
         if self.shadows is not None:
             self.shadows.refresh()
         kw = {"valid_mean": True} if self.pad_rows else {}
+        if self.criterion is not None:
+            kw["criterion"] = self.criterion
         feature, mask, labels = self.static
         if self.autocast_dtype is not None:
             with torch.autocast("cuda", dtype=self.autocast_dtype, cache_enabled=False):
@@ -2790,6 +2906,7 @@ class GraphedUnimodalStep(StepState):
     def __call__(self, batch, global_rows=None):
         """`global_rows`: GraphedTargetStep.__call__'s -- the real rows all ranks hold in this micro-step; pad_rows under an active exchange only"""
         feature, mask, labels = batch
+        check_criterion_rows("GraphedUnimodalStep", self.criterion, global_rows)
         rows = b = self.static[0].shape[0]
         padding = self.pad_rows and feature.dim() == self.static[0].dim() and feature.shape[0] != rows
         if padding:

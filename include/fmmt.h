@@ -537,6 +537,10 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
 #include "fmmt_stats.h"
 /* The text encoder on real tokens only (token layout of a padding mask, the unpack of packed rows, the attention core's ragged mode, the sublayer tails' row map): likewise, held to _lib.TOKENS_SIGNATURES. */
 #include "fmmt_tokens.h"
+/* The training loss as a value a run chooses -- class-weighted, label-smoothed cross-entropy, one launch per direction (fmmt_ce_fwd / _bwd), and the
+ * pooling head with that loss behind its classifier (fmmt_pool_head_fwd_crit / _bwd_crit): likewise, held to _lib.LOSS_SIGNATURES.  Limits stated
+ * there: den == 0 gives loss 0 and zero gradients (torch: NaN); the evaluation loss (fmmt_eval_accumulate) stays the plain cross-entropy. */
+#include "fmmt_loss.h"
 
 #ifdef __cplusplus
 }
