@@ -200,6 +200,13 @@ LOSS_SIGNATURES = {
     "fmmt_pool_head_fwd_crit": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _u64, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _sz, _p]),
     "fmmt_pool_head_bwd_crit": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
+# include/fmmt_route.h, one to one: a fifteenth table and header -- which kernel family a GEMM launch takes, answered on the host by the dispatch itself
+# (tests/test_gemm_routes_cpu.py holds table, header, the ROUTE_* values below and the library together)
+ROUTE_SIGNATURES = {
+    "fmmt_linear_fwd_route": (_i, [_i] * 17),
+    "fmmt_linear_wgrad_route": (_i, [_i] * 10),
+}
+ROUTE_MODE_FWD, ROUTE_MODE_SEG3_N, ROUTE_MODE_SEG3_K, ROUTE_MODE_SPLITK = 0, 1, 2, 3
 CE_MAXNL, CE_MAXB = 8, 65536          # include/fmmt_loss.h: the limits of fmmt_ce_fwd / _bwd
 RAGGED = 0x800          # include/fmmt_tokens.h FMMT_RAGGED: the dtype flag fmmt_mha_fwd_ragged / _bwd_ragged ask for
 
@@ -223,7 +230,7 @@ def load():
         raise FmmtError(f"{LIB_PATH} is missing: build it with `python -m facialmmt_amd.build` "
                         f"(or __graft_entry__.build()); there is no CPU / PyTorch fallback for the hot path")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + list(TOKENS_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(POOL_HEAD_SIGNATURES.items()) + list(RAGGED_SIGNATURES.items()) + list(EVAL_COLLECT_SIGNATURES.items()) + list(POOL_HEAD_ROWS_SIGNATURES.items()) + list(GUARD_SIGNATURES.items()) + list(DIGEST_SIGNATURES.items()) + list(EVAL_SHARD_SIGNATURES.items()) + list(JITTER_SIGNATURES.items()) + list(AUG_SIGNATURES.items()) + list(GROUPS_SIGNATURES.items()) + list(STATS_SIGNATURES.items()) + list(TOKENS_SIGNATURES.items()) + list(LOSS_SIGNATURES.items()) + list(ROUTE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

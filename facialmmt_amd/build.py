@@ -29,7 +29,7 @@ def build(force: bool = False, verbose: bool = True, tag: str = "") -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     tag = tag or os.environ.get("FMMT_BUILD_TAG", "")
     csrc = os.environ.get("FMMT_CSRC_DIR", CSRC) if tag else CSRC      # a tagged build may come from another source tree (an earlier commit)
-    headers = sorted(glob.glob(os.path.join(csrc, "*.h"))) + [os.path.join(csrc, "..", "..", "include", h) for h in ("fmmt.h", "fmmt_pool_head.h", "fmmt_ragged.h", "fmmt_eval_collect.h", "fmmt_pool_head_rows.h", "fmmt_guard.h", "fmmt_digest.h", "fmmt_eval_shard.h", "fmmt_jitter.h", "fmmt_aug.h", "fmmt_groups.h", "fmmt_stats.h", "fmmt_tokens.h", "fmmt_loss.h")]
+    headers = sorted(glob.glob(os.path.join(csrc, "*.h"))) + [os.path.join(csrc, "..", "..", "include", h) for h in ("fmmt.h", "fmmt_pool_head.h", "fmmt_ragged.h", "fmmt_eval_collect.h", "fmmt_pool_head_rows.h", "fmmt_guard.h", "fmmt_digest.h", "fmmt_eval_shard.h", "fmmt_jitter.h", "fmmt_aug.h", "fmmt_groups.h", "fmmt_stats.h", "fmmt_tokens.h", "fmmt_loss.h", "fmmt_route.h")]
     objdir = os.path.join(HERE, "build_" + tag if tag else "build")
     out = os.path.join(HERE, f"libfmmt_hip_{tag}.so") if tag else OUT
     os.makedirs(objdir, exist_ok=True)

@@ -999,10 +999,11 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
 }
 
 template <int BN, int BK, int NBUF, bool BATCH, bool HASOP, bool PIPE = false>
-int launch_p256_b(const LinArgs& a, hipStream_t st) {
+int launch_p256_b(const LinArgs& a, hipStream_t st, int* route) {
     constexpr size_t lds = (size_t)NBUF * (BN + 256) * BK * 2 + 2 * 256 * sizeof(float) + (BN == 256 ? 8 * 16 * 144 : 2 * (BN == 192 ? 32 : 16) * (BN * 2 + 16));   // ring, bias slabs, epilogue scratch (BN = 256: wave-private slabs)
     static_assert(lds <= 160 * 1024, "LDS");
     static FmmtLdsOnce lds_once;
+    if (route) { *route = (BN == 256 ? FMMT_ROUTE_P256_256 : BN == 192 ? FMMT_ROUTE_P256_192 : FMMT_ROUTE_P256_128) + (HASOP ? 2 : PIPE ? 1 : 0); return 0; }
     if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_nt_p256_kernel<BN, BK, NBUF, BATCH, HASOP, PIPE>), (int)lds)) return rc_;
     LinArgs p = a;
     p.tiles_m = (a.M + 255) / 256;
@@ -1012,19 +1013,19 @@ int launch_p256_b(const LinArgs& a, hipStream_t st) {
     return 0;
 }
 template <int BN, int BK, int NBUF>
-int launch_p256(const LinArgs& a, hipStream_t st) {
+int launch_p256(const LinArgs& a, hipStream_t st, int* route) {
     if constexpr (BN != 256) {
         // launches with an M x N epilogue operand or a DropPath scale: operand prefetched into registers (48 / 32 of them:
         // no room beside the 128 accumulators of the 256-wide tile).  (Operand-free launches that store directly, K > 1536, were tried
         // on this instantiation as well: against the pipelined loop below it loses, 135 -> 127 us, same call.)
-        if (a.res || a.aux || a.rowscale) return launch_p256_b<BN, BK, NBUF, true, true>(a, st);
+        if (a.res || a.aux || a.rowscale) return launch_p256_b<BN, BK, NBUF, true, true>(a, st, route);
     }
     // Pipelined fragment reads + DMA pieces in groups (PIPE), for K >= 384.  Same-call A/B against the plain loop, us per
     // launch: 31360 x 2304 x 768 124 -> 115, 31360 x 3072 x 768 150 -> 141, 31360 x 768 x 768 44.4 -> 41.2, 125440 x 1536 x 384
     // (256-wide tile, one group) 190 -> 178, 125440 x 384 x 384 52.7 -> 50.2, 125440 x 1152 x 384 / 384 x 1536 / 384 x 1152 +-1 %;
     // K = 192 (three K steps per tile: the late pieces are waited for) 210 -> 220, stays on the plain loop.
-    if (a.K >= 384) return launch_p256_b<BN, BK, NBUF, true, false, true>(a, st);
-    return launch_p256_b<BN, BK, NBUF, true, false>(a, st);
+    if (a.K >= 384) return launch_p256_b<BN, BK, NBUF, true, false, true>(a, st, route);
+    return launch_p256_b<BN, BK, NBUF, true, false>(a, st, route);
 }
 
 // Tile choice for the persistent kernel: the widest channel tile that divides N, unless a narrower one fills the last
@@ -1069,11 +1070,21 @@ int p256_plan(const LinArgs& a) {
     return best;
 }
 
+// the FMMT_ROUTE_* value of a linear_nt_kernel instantiation (BN = 96 / 128 share one)
+template <typename T, int BM, int BK, int NBUF, bool GLDS, bool SEG>
+constexpr int nt_route() {
+    if (sizeof(T) == 4) return BM == 64 ? FMMT_ROUTE_NT64_F32 : FMMT_ROUTE_NT128_F32;
+    if (BM == 32) return (SEG ? FMMT_ROUTE_NT_SEG3 : FMMT_ROUTE_NT_QUARTER) + (NBUF == 4 ? 1 : 0);
+    if (BM == 64) return NBUF == 1 ? (BK == 96 ? FMMT_ROUTE_NT64_K96 : FMMT_ROUTE_NT64_K64) : GLDS ? (NBUF == 4 ? FMMT_ROUTE_NT64_DMA_R4 : FMMT_ROUTE_NT64_DMA)
+                                   : BK == 64 ? FMMT_ROUTE_NT64_BK64 : FMMT_ROUTE_NT64_BK32;
+    return NBUF == 1 ? (BK == 96 ? FMMT_ROUTE_NT128_K96 : FMMT_ROUTE_NT128_K64) : GLDS ? FMMT_ROUTE_NT128_DMA : BK == 64 ? FMMT_ROUTE_NT128_BK64 : FMMT_ROUTE_NT128_BK32;
+}
 template <typename T, int BM, int BN, int BK, int NBUF, bool GLDS = false, bool SEG = false>
-int launch_nt(const LinArgs& a, hipStream_t st) {
+int launch_nt(const LinArgs& a, hipStream_t st, int* route) {
     constexpr int VEC = Vec<T>::N;
     constexpr size_t lds = (size_t)NBUF * (BM + BN) * (GLDS ? BK : BK + VEC) * sizeof(T);
     static FmmtLdsOnce lds_once;
+    if (route) { *route = nt_route<T, BM, BK, NBUF, GLDS, SEG>(); return 0; }
     if (lds > 65536) {
         if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_nt_kernel<T, BM, BN, BK, NBUF, GLDS, SEG>), (int)lds)) return rc_;
     }
@@ -1088,14 +1099,14 @@ int launch_nt(const LinArgs& a, hipStream_t st) {
 }
 
 template <typename T, int BM, int BN>
-int dispatch_nt_bk(const LinArgs& a, hipStream_t st) {
+int dispatch_nt_bk(const LinArgs& a, hipStream_t st, int* route) {
     if constexpr (sizeof(T) == 2) {
         // Swin stage 0: one K step.  (64- and 256-row tiles measured: no gain / -35 %.)  These launches are HBM streams
         // (40-70 FLOP/B); epilogue-shaped stores alone reach 5.5 TB/s on this part (profiles/r01_hbm_calibration.txt), what
         // holds a single-step workgroup at ~3 TB/s is its load -> LDS -> MFMA -> store chain with nothing to overlap, so
         // occupancy is what counts (NtWaves above); the fc1 + GELU + pre-activation launch is the only one still on it.
-        if (!a.ksplit && a.K == 96) return launch_nt<T, BM, BN, 96, 1>(a, st);
-        if (!a.ksplit && a.K <= 64) return launch_nt<T, BM, BN, 64, 1>(a, st);     // PatchEmbed (K = 48)
+        if (!a.ksplit && a.K == 96) return launch_nt<T, BM, BN, 96, 1>(a, st, route);
+        if (!a.ksplit && a.K <= 64) return launch_nt<T, BM, BN, 64, 1>(a, st, route);     // PatchEmbed (K = 48)
         // measured on MI355X (tools/probes/gemm_bench.py, sum over the bench shapes): BK=64 5.33 ms vs BK=32 5.88 ms
         // direct global->LDS DMA staging: measured +7 % over register staging summed over the bench shapes, up to
         // +25 % on the K >= 768 ones (971 TF/s on 31360x768x3072)
@@ -1105,14 +1116,14 @@ int dispatch_nt_bk(const LinArgs& a, hipStream_t st) {
             // co-residency (1328 x 3072 x 768: 15 -> 21 us), and at K = 768 it is a wash.
             if constexpr (BM == 64) {
                 const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-                if (a.K >= 2048 && tiles <= 256) return launch_nt<T, BM, BN, 64, 4, true>(a, st);
+                if (a.K >= 2048 && tiles <= 256) return launch_nt<T, BM, BN, 64, 4, true>(a, st, route);
             }
-            return launch_nt<T, BM, BN, 64, 2, true>(a, st);
+            return launch_nt<T, BM, BN, 64, 2, true>(a, st, route);
         }
-        if (a.K % 64 == 0 && (!a.ksplit || a.ksplit % 64 == 0)) return launch_nt<T, BM, BN, 64, 2>(a, st);
-        return launch_nt<T, BM, BN, 32, 2>(a, st);
+        if (a.K % 64 == 0 && (!a.ksplit || a.ksplit % 64 == 0)) return launch_nt<T, BM, BN, 64, 2>(a, st, route);
+        return launch_nt<T, BM, BN, 32, 2>(a, st, route);
     } else {
-        return launch_nt<T, BM, BN, 16, 2>(a, st);                                 // fp32 parity path
+        return launch_nt<T, BM, BN, 16, 2>(a, st, route);                                 // fp32 parity path
     }
 }
 
@@ -1164,7 +1175,7 @@ int ph_plan(const LinArgs& a, int* epi3) {
 }
 
 template <typename T>
-int dispatch_nt(const LinArgs& a, hipStream_t st) {
+int dispatch_nt(const LinArgs& a, hipStream_t st, int* route) {
     // BN = 96 when it tiles N exactly and 128 would not (C = 96, 288, 192, 576 ...)
     const bool n96 = (a.N % 96 == 0) && (a.N % 128 != 0);
     // few-token problems (cross-modal encoder: 152..1280 rows; embedding head: 640 rows) use 64-row tiles so
@@ -1184,21 +1195,21 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             constexpr int SMALL_R4K = 2048;                // four-buffer ring from this K
             const int tiles = ((a.M + 63) / 64) * ((a.N + 127) / 128);
             if (tiles < SMALL_TILES && a.N % 64 == 0 && a.K % 64 == 0 && a.K >= 128 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
-                if (a.K >= SMALL_R4K) return launch_nt<T, 32, 64, 64, 4, true>(a, st);
-                return launch_nt<T, 32, 64, 64, 2, true>(a, st);
+                if (a.K >= SMALL_R4K) return launch_nt<T, 32, 64, 64, 4, true>(a, st, route);
+                return launch_nt<T, 32, 64, 64, 2, true>(a, st, route);
             }
         }
-        return n96 ? dispatch_nt_bk<T, 64, 96>(a, st) : dispatch_nt_bk<T, 64, 128>(a, st);
+        return n96 ? dispatch_nt_bk<T, 64, 96>(a, st, route) : dispatch_nt_bk<T, 64, 128>(a, st, route);
     }
     if constexpr (sizeof(T) == 2) {
         int epi3 = 2;
         if (const int ph = ph_plan(a, &epi3)) {
-            if (ph == 1) return launch_ph<2>(a, st);
-            if (ph == 4) return epi3 == 6 ? launch_ph3<6, true, 4>(a, st) : epi3 == 5 ? launch_ph3<5, true, 4>(a, st) : launch_ph3<2, true, 4>(a, st);
-            return epi3 == 3 ? launch_ph3<3>(a, st) : epi3 == 6 ? launch_ph3<6>(a, st) : epi3 == 5 ? launch_ph3<5>(a, st) : launch_ph3<2>(a, st);
+            if (ph == 1) return launch_ph<2>(a, st, route);
+            if (ph == 4) return epi3 == 6 ? launch_ph3<6, true, 4>(a, st, route) : epi3 == 5 ? launch_ph3<5, true, 4>(a, st, route) : launch_ph3<2, true, 4>(a, st, route);
+            return epi3 == 3 ? launch_ph3<3>(a, st, route) : epi3 == 6 ? launch_ph3<6>(a, st, route) : epi3 == 5 ? launch_ph3<5>(a, st, route) : launch_ph3<2>(a, st, route);
         }
         if (const int bn = p256_plan(a))
-            return bn == 256 ? launch_p256<256, 64, 2>(a, st) : bn == 192 ? launch_p256<192, 64, 2>(a, st) : launch_p256<128, 64, 3>(a, st);
+            return bn == 256 ? launch_p256<256, 64, 2>(a, st, route) : bn == 192 ? launch_p256<192, 64, 2>(a, st, route) : launch_p256<128, 64, 3>(a, st, route);
         // measured (tools/probes/gemm_bench.py): +8 % on the 125440-token stage-2 shapes (K = 384: 496 -> 540 TF/s),
         // -4 % on the 31360-token stage-3 shapes (tile quantisation at one workgroup per CU) -> only for M >= 65536
         constexpr int DEEP_MINM = 65536, DEEP_MINK = 96;
@@ -1210,7 +1221,7 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             constexpr size_t lds = (size_t)3 * (256 + 128) * 64 * 2;
             constexpr size_t lds96 = (size_t)3 * (256 + 96) * 32 * 2;
             static FmmtLdsOnce lds_once[7];
-            {
+            if (!route) {
                 const void* fns[] = {reinterpret_cast<const void*>(&linear_nt_deep_kernel),
                                      reinterpret_cast<const void*>(&linear_nt_deep32_kernel<0, 128>),
                                      reinterpret_cast<const void*>(&linear_nt_deep32_kernel<6, 128>),
@@ -1224,11 +1235,13 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             }
             LinArgs p = a;
             p.tiles_m = (a.M + 255) / 256;
-                    if (n96) {
+            // one launch site per instantiation; with `route` set it names itself instead of launching
+#define FMMT_DEEP_LAUNCH(R, KERNEL, LDS) do { if (route) { *route = R; return 0; } hipLaunchKernelGGL(KERNEL, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS, st, p); } while (0)
+            if (n96) {
                 p.tiles_n = a.N / 96;
-                if (a.K == 192) hipLaunchKernelGGL((linear_nt_deep32_kernel<6, 96>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds96, st, p);
-                else if (a.K == 96) hipLaunchKernelGGL((linear_nt_deep32_kernel<3, 96>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds96, st, p);
-                else hipLaunchKernelGGL((linear_nt_deep32_kernel<0, 96>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds96, st, p);
+                if (a.K == 192) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K192_N96, (linear_nt_deep32_kernel<6, 96>), lds96);
+                else if (a.K == 96) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K96_N96, (linear_nt_deep32_kernel<3, 96>), lds96);
+                else FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_N96, (linear_nt_deep32_kernel<0, 96>), lds96);
                 FMMT_CHECK_LAUNCH();
                 return 0;
             }
@@ -1237,18 +1250,19 @@ int dispatch_nt(const LinArgs& a, hipStream_t st) {
             // where the epilogue is a large share of a tile's life -- GELU / GELU' launches (0.388 -> 0.340 ms) and
             // K = 384 (384x384: 0.069 -> 0.057 ms); the K-step-64 kernel keeps a 2-4 % edge on plain K >= 1152.
             if (a.epi != 0 || a.K <= 512 || a.K % 64 != 0) {
-                if (a.K == 192) hipLaunchKernelGGL((linear_nt_deep32_kernel<6, 128>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds / 2, st, p);
-                else if (a.K == 96) hipLaunchKernelGGL((linear_nt_deep32_kernel<3, 128>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds / 2, st, p);
-                else hipLaunchKernelGGL((linear_nt_deep32_kernel<0, 128>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds / 2, st, p);
+                if (a.K == 192) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K192_N128, (linear_nt_deep32_kernel<6, 128>), lds / 2);
+                else if (a.K == 96) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K96_N128, (linear_nt_deep32_kernel<3, 128>), lds / 2);
+                else FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_N128, (linear_nt_deep32_kernel<0, 128>), lds / 2);
             } else {
-                hipLaunchKernelGGL(linear_nt_deep_kernel, dim3(p.tiles_m * p.tiles_n), dim3(512), lds, st, p);
+                FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP, linear_nt_deep_kernel, lds);
             }
+#undef FMMT_DEEP_LAUNCH
             FMMT_CHECK_LAUNCH();
             return 0;
         }
     }
     // (256-row tiles with 4 waves measured: -30 % on the stage-2/3 shapes -- one workgroup per CU)
-    return n96 ? dispatch_nt_bk<T, 128, 96>(a, st) : dispatch_nt_bk<T, 128, 128>(a, st);
+    return n96 ? dispatch_nt_bk<T, 128, 96>(a, st, route) : dispatch_nt_bk<T, 128, 128>(a, st, route);
 }
 
 // y = T(sum_s part[s] + bias) for the split-K path
@@ -1518,10 +1532,14 @@ void linear_tn_kernel(TnArgs p) {
 }
 
 template <typename T, int BMS, bool FEW = false, int PF = 1>
-int launch_tn(const TnArgs& a, dim3 grid, hipStream_t st) {
+int launch_tn(const TnArgs& a, dim3 grid, hipStream_t st, int* route) {
     constexpr int VEC = Vec<T>::N;
     constexpr size_t lds = (size_t)4 * BMS * (sizeof(T) == 2 ? 128 : 128 + VEC) * sizeof(T) + (256 / (128 / VEC)) * 128 * sizeof(float);
     static FmmtLdsOnce lds_once;
+    if (route) {
+        *route = sizeof(T) == 4 ? FMMT_ROUTE_TN_F32 : FEW ? FMMT_ROUTE_TN_REG32_FEW : BMS == 64 ? FMMT_ROUTE_TN_REG64 : FMMT_ROUTE_TN_REG32;
+        return 0;
+    }
     if (lds > 65536) {
         if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_kernel<T, BMS, FEW, PF>), (int)lds)) return rc_;
     }
@@ -1665,9 +1683,10 @@ __global__ __launch_bounds__(512) void linear_tn_few_kernel(TnArgs p) {
     }
 }
 
-int launch_tn_few(int M, int N, int K, const void* dy, int lddy, const void* x, int ldx, float* dw, float* db, int* hdr, hipStream_t st) {
+int launch_tn_few(int M, int N, int K, const void* dy, int lddy, const void* x, int ldx, float* dw, float* db, int* hdr, hipStream_t st, int* route) {
     constexpr int lds = 80 * 1024;
     static FmmtLdsOnce lds_once;
+    if (route) { *route = FMMT_ROUTE_TN_FEW; return 0; }
     if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_few_kernel), lds)) return rc_;
     TnArgs a{M, N, K, dy, lddy, x, ldx, dw, db, nullptr, 1, K / 64, (M + 7) / 8, N / 64, 0, hdr, 1};
     hipLaunchKernelGGL(linear_tn_few_kernel, dim3((N / 64) * (K / 64)), dim3(512), lds, st, a);
@@ -2091,10 +2110,15 @@ __global__ __launch_bounds__(512) void linear_tn_dma_kernel(TnArgs p) {
 }
 
 template <int TNn, int TKk, int NBUF, int WN, bool SCALED = false>
-int launch_tn_dma(const TnArgs& a, int grid, hipStream_t st) {
+int launch_tn_dma(const TnArgs& a, int grid, hipStream_t st, int* route) {
     constexpr size_t lds = (size_t)NBUF * 32 * (TNn + TKk) * 2 + (SCALED ? 4096 + 64 : 0);
     static_assert(lds <= 160 * 1024, "LDS");
     static FmmtLdsOnce lds_once;
+    if (route) {
+        *route = TNn == 384 ? FMMT_ROUTE_TN_DMA_384 : TNn == 256 ? (SCALED ? FMMT_ROUTE_TN_DMA_256_SCALED : FMMT_ROUTE_TN_DMA_256)
+                                                                 : (SCALED ? FMMT_ROUTE_TN_DMA_192_SCALED : FMMT_ROUTE_TN_DMA_192);
+        return 0;
+    }
     if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_dma_kernel<TNn, TKk, NBUF, WN, SCALED>), (int)lds)) return rc_;
     hipLaunchKernelGGL((linear_tn_dma_kernel<TNn, TKk, NBUF, WN, SCALED>), dim3(grid), dim3(512), lds, st, a);
     FMMT_CHECK_LAUNCH();
@@ -2202,6 +2226,35 @@ TnPlan tn_plan(int M, int N, int K, int dtype) {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The entry points' bodies take `int* route` (include/fmmt_route.h): NULL launches; non-NULL runs the same validation and dispatch and stores the
+// FMMT_ROUTE_* value at the place where the launch would be issued -- no HIP call on that path.
+
+// Every epilogue moves 16-byte vectors at row * ld + column (nt_epilogue / _slab / _wslab, the p256 slab stores, the buffer stores of gemm_ph.h /
+// gemm_ph3.h; DESIGN.md "Leading dimensions of the GEMMs"): N and every ld of a present M x N operand keep each row 16-byte aligned.
+int linear_fwd_impl(int dtype, int M, int N, int K,
+                    const void* x, int ldx, const void* w, int ldw, const float* bias,
+                    void* y, int ldy, void* y_pre,
+                    int epi, const void* aux, int ldaux,
+                    const void* res, int ldres, const float* rowscale, int rows_per_scale,
+                    void* stream, int* route) {
+    if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
+    const int vec = dtype == FMMT_BF16 ? 8 : 4;
+    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
+    if (K % vec || N % vec || ldx % vec || ldw % vec || ldy % vec) return FMMT_EINVAL;
+    if (ldx < K || ldw < K || ldy < N) return FMMT_EINVAL;
+    if (epi < 0 || epi > FMMT_EPI_MUL_AUX) return FMMT_EINVAL;
+    if ((epi == FMMT_EPI_GELU_BWD || epi == FMMT_EPI_MUL_AUX) && !aux) return FMMT_EINVAL;
+    if (aux && (ldaux % vec || ldaux < N)) return FMMT_EINVAL;
+    if (res && (ldres % vec || ldres < N)) return FMMT_EINVAL;
+    if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
+    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (bias && !aligned16(bias)) ||
+        (res && !aligned16(res)) || (aux && !aligned16(aux)) || (y_pre && !aligned16(y_pre)))
+        return FMMT_EALIGN;
+    LinArgs a{M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, 0, 0, 0, 0, nullptr};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    return dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st, route) : dispatch_nt<float>(a, st, route);
+}
+
 }  // namespace
 
 extern "C" int fmmt_linear_fwd(int dtype, int M, int N, int K,
@@ -2210,20 +2263,7 @@ extern "C" int fmmt_linear_fwd(int dtype, int M, int N, int K,
                                int epi, const void* aux, int ldaux,
                                const void* res, int ldres, const float* rowscale, int rows_per_scale,
                                void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
-    const int vec = dtype == FMMT_BF16 ? 8 : 4;
-    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
-    if (K % vec || N % 4 || ldx % vec || ldw % vec || ldy % 4) return FMMT_EINVAL;
-    if (epi < 0 || epi > FMMT_EPI_MUL_AUX) return FMMT_EINVAL;
-    if ((epi == FMMT_EPI_GELU_BWD || epi == FMMT_EPI_MUL_AUX) && (!aux || ldaux % 4)) return FMMT_EINVAL;
-    if (res && ldres % 4) return FMMT_EINVAL;
-    if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
-    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (bias && !aligned16(bias)) ||
-        (res && !aligned16(res)) || (aux && !aligned16(aux)) || (y_pre && !aligned16(y_pre)))
-        return FMMT_EALIGN;
-    LinArgs a{M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, 0, 0, 0, 0, nullptr};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st) : dispatch_nt<float>(a, st);
+    return linear_fwd_impl(dtype, M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, stream, nullptr);
 }
 
 // Few-token Linear over THREE weights in one launch (MELDTransEncoder's query / key / value, modules/Transformer.py:64-103: three nn.Linear over
@@ -2232,12 +2272,15 @@ extern "C" int fmmt_linear_fwd(int dtype, int M, int N, int K,
 //   seg_mode 2 (along K): y = sum_s x[:, s * K/3 : (s + 1) * K/3] @ w_s^T            w_s [N][K/3]   (no bias)
 // bf16, the direct-to-LDS quarter-tile kernels only (the shapes dispatch_nt sends there: tokens <= 4096, few tiles); anything else: FMMT_EINVAL and
 // the caller issues three fmmt_linear_fwd calls.
-extern "C" int fmmt_linear_fwd_seg3(int dtype, int M, int N, int K, const void* x, int ldx, const void* w0, const void* w1, const void* w2, int ldw,
-                                    int seg_mode, const float* bias0, const float* bias1, const float* bias2, void* y, int ldy, void* stream) {
+namespace {
+int seg_mode_cols(int seg_mode, int K) { return seg_mode == 2 ? K / 3 : K; }   // row width of one of the three weights
+int linear_fwd_seg3_impl(int dtype, int M, int N, int K, const void* x, int ldx, const void* w0, const void* w1, const void* w2, int ldw,
+                         int seg_mode, const float* bias0, const float* bias1, const float* bias2, void* y, int ldy, void* stream, int* route) {
     if (dtype != FMMT_BF16 || M <= 0 || N <= 0 || K <= 0 || (seg_mode != 1 && seg_mode != 2)) return FMMT_EINVAL;
     if (!x || !w0 || !w1 || !w2 || !y) return FMMT_EINVAL;
     const int seg = seg_mode == 1 ? N / 3 : K / 3;
-    if ((seg_mode == 1 ? N : K) % 3 || seg % 64 || N % 64 || K % 64 || K < 128 || ldx % 8 || ldw % 8 || ldy % 4 || M > 4096) return FMMT_EINVAL;
+    if ((seg_mode == 1 ? N : K) % 3 || seg % 64 || N % 64 || K % 64 || K < 128 || ldx % 8 || ldw % 8 || ldy % 8 || M > 4096) return FMMT_EINVAL;
+    if (ldx < K || ldw < seg_mode_cols(seg_mode, K) || ldy < N) return FMMT_EINVAL;
     if (seg_mode == 2 && (bias0 || bias1 || bias2)) return FMMT_EINVAL;
     if (!aligned16(x) || !aligned16(w0) || !aligned16(w1) || !aligned16(w2) || !aligned16(y)) return FMMT_EALIGN;
     if (((M + 63) / 64) * ((N + 127) / 128) >= 256) return FMMT_EINVAL;                 // dispatch_nt's few-tile rule: larger problems do not come here
@@ -2249,8 +2292,14 @@ extern "C" int fmmt_linear_fwd_seg3(int dtype, int M, int N, int K, const void* 
     a.wseg = seg;
     a.wseg_mode = seg_mode;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (K >= 2048) return launch_nt<bf16, 32, 64, 64, 4, true, true>(a, st);
-    return launch_nt<bf16, 32, 64, 64, 2, true, true>(a, st);
+    if (K >= 2048) return launch_nt<bf16, 32, 64, 64, 4, true, true>(a, st, route);
+    return launch_nt<bf16, 32, 64, 64, 2, true, true>(a, st, route);
+}
+}  // namespace
+
+extern "C" int fmmt_linear_fwd_seg3(int dtype, int M, int N, int K, const void* x, int ldx, const void* w0, const void* w1, const void* w2, int ldw,
+                                    int seg_mode, const float* bias0, const float* bias1, const float* bias2, void* y, int ldy, void* stream) {
+    return linear_fwd_seg3_impl(dtype, M, N, K, x, ldx, w0, w1, w2, ldw, seg_mode, bias0, bias1, bias2, y, ldy, stream, nullptr);
 }
 
 extern "C" size_t fmmt_linear_splitk_workspace(int M, int N, int K) {
@@ -2259,14 +2308,18 @@ extern "C" size_t fmmt_linear_splitk_workspace(int M, int N, int K) {
     return ks ? (size_t)splits * M * N * sizeof(float) : 0;
 }
 
-extern "C" int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void* x, int ldx, const void* w, int ldw,
-                                      const float* bias, void* y, int ldy, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+namespace {
+int linear_fwd_splitk_impl(int dtype, int M, int N, int K, const void* x, int ldx, const void* w, int ldw,
+                           const float* bias, void* y, int ldy, void* workspace, size_t workspace_bytes,
+                           void* stream, int* route) {
     if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
     if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
     const int vec = dtype == FMMT_BF16 ? 8 : 4;
-    if (K % vec || N % 4 || ldx % vec || ldw % vec) return FMMT_EINVAL;
-    if (!aligned16(x) || !aligned16(w) || !aligned16(workspace)) return FMMT_EALIGN;
+    // the finish kernel stores single elements at m * ldy + n and the partials are f32x4 at m * N + n: any N % 4 and any pitch that holds a row
+    // would be addressable; N and ldy are held to fmmt_linear_fwd's rule (% 8 in bf16) so that one shape and one output view serve both entry points
+    if (K % vec || N % vec || ldx % vec || ldw % vec) return FMMT_EINVAL;
+    if (!y || ldy < N || ldy % vec || ldx < K || ldw < K) return FMMT_EINVAL;
+    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || !aligned16(workspace)) return FMMT_EALIGN;
     int ks;
     const int splits = splitk_plan(M, N, K, &ks);
     if (!ks) return FMMT_EINVAL;                            // not a split-K shape: use fmmt_linear_fwd
@@ -2274,7 +2327,8 @@ extern "C" int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void
     LinArgs a{M, N, K, x, ldx, w, ldw, nullptr, nullptr, N, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, ks,
               reinterpret_cast<float*>(workspace)};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (int rc = (dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st) : dispatch_nt<float>(a, st))) return rc;
+    if (int rc = (dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st, route) : dispatch_nt<float>(a, st, route))) return rc;
+    if (route) return 0;                                   // the contraction's route; the finish below is one kernel for every shape
     const size_t total = (size_t)M * N;
     if (dtype == FMMT_BF16)
         hipLaunchKernelGGL(splitk_finish_kernel<bf16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, splits, M, N, bias, (bf16*)y, ldy);
@@ -2282,6 +2336,35 @@ extern "C" int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void
         hipLaunchKernelGGL(splitk_finish_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, splits, M, N, bias, (float*)y, ldy);
     FMMT_CHECK_LAUNCH();
     return 0;
+}
+}  // namespace
+
+extern "C" int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void* x, int ldx, const void* w, int ldw,
+                                      const float* bias, void* y, int ldy, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return linear_fwd_splitk_impl(dtype, M, N, K, x, ldx, w, ldw, bias, y, ldy, workspace, workspace_bytes, stream, nullptr);
+}
+
+// fake operands of the route queries: present, 16-byte aligned, never dereferenced (no launch is issued with `route` set)
+namespace {
+void* route_ptr(int present) { return present ? reinterpret_cast<void*>(static_cast<uintptr_t>(4096)) : nullptr; }
+}  // namespace
+
+extern "C" int fmmt_linear_fwd_route(int dtype, int M, int N, int K, int ldx, int ldw, int ldy, int has_bias, int has_y_pre, int epi,
+                                     int has_aux, int ldaux, int has_res, int ldres, int has_rowscale, int rows_per_scale, int mode) {
+    int route = 0, rc;
+    void* const pp = route_ptr(1);
+    const float* const bias = reinterpret_cast<const float*>(route_ptr(has_bias));
+    if (mode == FMMT_ROUTE_MODE_FWD)
+        rc = linear_fwd_impl(dtype, M, N, K, pp, ldx, pp, ldw, bias, pp, ldy, route_ptr(has_y_pre), epi, route_ptr(has_aux), ldaux, route_ptr(has_res), ldres,
+                             reinterpret_cast<const float*>(route_ptr(has_rowscale)), rows_per_scale, nullptr, &route);
+    else if (mode == FMMT_ROUTE_MODE_SEG3_N || mode == FMMT_ROUTE_MODE_SEG3_K)
+        rc = linear_fwd_seg3_impl(dtype, M, N, K, pp, ldx, pp, pp, pp, ldw, mode, bias, bias, bias, pp, ldy, nullptr, &route);
+    else if (mode == FMMT_ROUTE_MODE_SPLITK)
+        rc = linear_fwd_splitk_impl(dtype, M, N, K, pp, ldx, pp, ldw, bias, pp, ldy, pp, ~(size_t)0, nullptr, &route);
+    else
+        return FMMT_EINVAL;
+    return rc ? rc : route;
 }
 
 namespace {
@@ -2357,10 +2440,10 @@ extern "C" size_t fmmt_linear_wgrad_workspace(int dtype, int M, int N, int K) {
 namespace {
 // the split contraction: part_w [splits][N][K], part_b [splits][N] or nullptr (splits == 1: these may be dw / db themselves)
 int launch_tn_plan(int dtype, int M, int N, int K, const void* dy, int lddy, const void* x, int ldx, float* part_w, float* part_b,
-                   const float* rowscale, int rows_per_scale, int x_epi, int* hdr, hipStream_t st) {
+                   const float* rowscale, int rows_per_scale, int x_epi, int* hdr, hipStream_t st, int* route) {
     if (x_epi != 0 && x_epi != FMMT_EPI_GELU) return FMMT_EINVAL;
     if (tn_few_ok(M, N, K, dtype) && !rowscale && !x_epi && lddy % 8 == 0 && ldx % 8 == 0)
-        return launch_tn_few(M, N, K, dy, lddy, x, ldx, part_w, part_b, hdr, st);     // one split: part_w / part_b may be dw / db themselves
+        return launch_tn_few(M, N, K, dy, lddy, x, ldx, part_w, part_b, hdr, st, route);     // one split: part_w / part_b may be dw / db themselves
     if (dtype == FMMT_BF16 && hdr && !x_epi && lddy % 8 == 0 && ldx % 8 == 0) {
         const TnPlan pd = tn_plan_dma(M, N, K);
         // scaled launches: the split's slice of the scale vector has to fit the 4 KB behind the ring
@@ -2368,35 +2451,36 @@ int launch_tn_plan(int dtype, int M, int N, int K, const void* dy, int lddy, con
         if (pd.tn && scaled_ok) {
             TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pd.tiles_k, pd.chunk, pd.tiles_n, 0, hdr, pd.splits, pd.npad};
             const int grid = pd.tiles_n * pd.tiles_k * pd.splits;
-            if (rowscale) return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2, true>(a, grid, st) : launch_tn_dma<192, 384, 4, 2, true>(a, grid, st);
-            if (pd.tk == 192) return launch_tn_dma<384, 192, 4, 4>(a, grid, st);
-            return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2>(a, grid, st) : launch_tn_dma<192, 384, 4, 2>(a, grid, st);
+            if (rowscale) return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2, true>(a, grid, st, route) : launch_tn_dma<192, 384, 4, 2, true>(a, grid, st, route);
+            if (pd.tk == 192) return launch_tn_dma<384, 192, 4, 4>(a, grid, st, route);
+            return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2>(a, grid, st, route) : launch_tn_dma<192, 384, 4, 2>(a, grid, st, route);
         }
     }
     const TnPlan pl = tn_plan(M, N, K, dtype);
     TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pl.tiles_k, pl.chunk, pl.tiles_n, x_epi == FMMT_EPI_GELU, hdr, pl.splits};
     dim3 grid(pl.tiles_n * pl.tiles_k * pl.splits);
     if (dtype == FMMT_BF16) {
-        if (M <= 4096) return launch_tn<bf16, 32, true>(a, grid, st);      // few-token problems: 32-token steps, one in flight
+        if (M <= 4096) return launch_tn<bf16, 32, true>(a, grid, st, route);      // few-token problems: 32-token steps, one in flight
         // measured (tools/probes/gemm_bench.py): 64-token steps win for the compute-heavy stage-2/3 shapes (+15-25 %),
         // 32-token steps (3 workgroups per CU) win for the HBM-bound multi-million-token stage-0/1 shapes.
         // Two token steps in flight (register sets R0/R1): measured +3..5 % on the stage-2/3 shapes, +3..11 % on the stage-0/1
         // ones, at unchanged occupancy (200 / 160 registers)
-        if (M <= 262144) return launch_tn<bf16, 64, false, 2>(a, grid, st);
-        return launch_tn<bf16, 32, false, 2>(a, grid, st);
+        if (M <= 262144) return launch_tn<bf16, 64, false, 2>(a, grid, st, route);
+        return launch_tn<bf16, 32, false, 2>(a, grid, st, route);
     }
-    return launch_tn<float, 16>(a, grid, st);
+    return launch_tn<float, 16>(a, grid, st, route);
 }
 }  // namespace
 
-extern "C" int fmmt_linear_wgrad_partials(int dtype, int M, int N, int K,
-                                          const void* dy, int lddy, const void* x, int ldx, int want_bias,
-                                          const float* rowscale, int rows_per_scale, int x_epi,
-                                          void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+int linear_wgrad_partials_impl(int dtype, int M, int N, int K,
+                               const void* dy, int lddy, const void* x, int ldx, int want_bias,
+                               const float* rowscale, int rows_per_scale, int x_epi,
+                               void* workspace, size_t workspace_bytes, void* stream, int* route) {
     if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
     if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
     const int vec = dtype == FMMT_BF16 ? 8 : 4;
-    if (N % vec || K % vec || lddy % vec || ldx % vec) return FMMT_EINVAL;
+    if (N % vec || K % vec || lddy % vec || ldx % vec || lddy < N || ldx < K) return FMMT_EINVAL;
     if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
     if (!aligned16(dy) || !aligned16(x) || !aligned16(workspace)) return FMMT_EALIGN;
     if (workspace_bytes < tn_ws_bytes(M, N, K, dtype)) return FMMT_EWORKSPACE;
@@ -2405,7 +2489,15 @@ extern "C" int fmmt_linear_wgrad_partials(int dtype, int M, int N, int K,
     float* part_b = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + TN_HDR);
     float* part_w = part_b + (size_t)smax * tn_rows(M, N, K, dtype);
     return launch_tn_plan(dtype, M, N, K, dy, lddy, x, ldx, part_w, want_bias ? part_b : nullptr, rowscale, rows_per_scale, x_epi, hdr,
-                          reinterpret_cast<hipStream_t>(stream));
+                          reinterpret_cast<hipStream_t>(stream), route);
+}
+}  // namespace
+
+extern "C" int fmmt_linear_wgrad_partials(int dtype, int M, int N, int K,
+                                          const void* dy, int lddy, const void* x, int ldx, int want_bias,
+                                          const float* rowscale, int rows_per_scale, int x_epi,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    return linear_wgrad_partials_impl(dtype, M, N, K, dy, lddy, x, ldx, want_bias, rowscale, rows_per_scale, x_epi, workspace, workspace_bytes, stream, nullptr);
 }
 
 extern "C" int fmmt_linear_wgrad_finish(int dtype, int M, int N, int K, float* dw, float* db,
@@ -2428,21 +2520,44 @@ extern "C" int fmmt_linear_wgrad_finish(int dtype, int M, int N, int K, float* d
     return 0;
 }
 
-extern "C" int fmmt_linear_wgrad(int dtype, int M, int N, int K,
-                                 const void* dy, int lddy, const void* x, int ldx,
-                                 float* dw, float* db, const float* rowscale, int rows_per_scale, int x_epi,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+int linear_wgrad_impl(int dtype, int M, int N, int K,
+                      const void* dy, int lddy, const void* x, int ldx,
+                      float* dw, float* db, const float* rowscale, int rows_per_scale, int x_epi,
+                      void* workspace, size_t workspace_bytes, void* stream, int* route) {
     if (!aligned16(dw)) return FMMT_EALIGN;
     const bool few = M > 0 && N > 0 && K > 0 && tn_few_ok(M, N, K, dtype) && !rowscale && !x_epi && lddy % 8 == 0 && ldx % 8 == 0;
     if (M > 0 && N > 0 && K > 0 && (dtype == FMMT_BF16 || dtype == FMMT_F32) && (few || tn_smax(M, N, K, dtype) == 1)) {
         // single split: the "partials" ARE the result -- let the contraction kernel write dw / db directly
         const int vec = dtype == FMMT_BF16 ? 8 : 4;
-        if (N % vec || K % vec || lddy % vec || ldx % vec) return FMMT_EINVAL;
+        if (N % vec || K % vec || lddy % vec || ldx % vec || lddy < N || ldx < K) return FMMT_EINVAL;
         if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
         if (!aligned16(dy) || !aligned16(x)) return FMMT_EALIGN;
-        return launch_tn_plan(dtype, M, N, K, dy, lddy, x, ldx, dw, db, rowscale, rows_per_scale, x_epi, nullptr, reinterpret_cast<hipStream_t>(stream));
+        return launch_tn_plan(dtype, M, N, K, dy, lddy, x, ldx, dw, db, rowscale, rows_per_scale, x_epi, nullptr, reinterpret_cast<hipStream_t>(stream), route);
     }
-    if (int rc = fmmt_linear_wgrad_partials(dtype, M, N, K, dy, lddy, x, ldx, db != nullptr, rowscale, rows_per_scale, x_epi,
-                                            workspace, workspace_bytes, stream)) return rc;
+    if (int rc = linear_wgrad_partials_impl(dtype, M, N, K, dy, lddy, x, ldx, db != nullptr, rowscale, rows_per_scale, x_epi,
+                                            workspace, workspace_bytes, stream, route)) return rc;
+    if (route) return 0;                                   // the contraction's route; the finish is one kernel for every shape
     return fmmt_linear_wgrad_finish(dtype, M, N, K, dw, db, workspace, workspace_bytes, stream);
+}
+}  // namespace
+
+extern "C" int fmmt_linear_wgrad(int dtype, int M, int N, int K,
+                                 const void* dy, int lddy, const void* x, int ldx,
+                                 float* dw, float* db, const float* rowscale, int rows_per_scale, int x_epi,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return linear_wgrad_impl(dtype, M, N, K, dy, lddy, x, ldx, dw, db, rowscale, rows_per_scale, x_epi, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int fmmt_linear_wgrad_route(int dtype, int M, int N, int K, int lddy, int ldx, int has_rowscale, int rows_per_scale, int x_epi, int mode) {
+    int route = 0, rc;
+    void* const pp = route_ptr(1);
+    const float* const rs = reinterpret_cast<const float*>(route_ptr(has_rowscale));
+    if (mode == 0)
+        rc = linear_wgrad_impl(dtype, M, N, K, pp, lddy, pp, ldx, reinterpret_cast<float*>(pp), reinterpret_cast<float*>(pp), rs, rows_per_scale, x_epi, pp, ~(size_t)0, nullptr, &route);
+    else if (mode == 1)
+        rc = linear_wgrad_partials_impl(dtype, M, N, K, pp, lddy, pp, ldx, 1, rs, rows_per_scale, x_epi, pp, ~(size_t)0, nullptr, &route);
+    else
+        return FMMT_EINVAL;
+    return rc ? rc : route;
 }

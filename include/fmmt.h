@@ -70,7 +70,15 @@ int fmmt_version(void);
  *   - FMMT_EPI_GELU_BWD: aux[M,N] (dtype) holds the saved pre-activation;
  *   - FMMT_EPI_GELU_DG: y_pre (may be NULL) receives gelu'(acc + bias); FMMT_EPI_MUL_AUX: aux[M,N] (dtype) holds that derivative.
  * The same entry point computes input gradients: dx[M,K] = dy[M,N] . (w^T)[K,N]^T with a transposed
- * copy of the weight.  K % 8 == 0 (bf16) / K % 4 == 0 (f32), N % 4 == 0.
+ * copy of the weight.
+ * Leading dimensions: every operand and output may be a view with a row pitch larger than its width (a slice of a packed buffer, a padded
+ * allocation); nothing outside the M x width region of an output is written, and what lies outside the region of an input may be read
+ * but never enters a result.  Every kernel moves whole 16-byte vectors at row * ld + column, so each ld keeps every row 16-byte aligned:
+ *   bf16: K, N, ldx, ldw, ldy and -- where the operand is present -- ldres, ldaux multiples of 8;
+ *   f32 : the same multiples of 4.
+ * Anything else returns FMMT_EINVAL before any launch (bf16 with N or an ld congruent to 4 mod 8 was accepted until the strided GEMM tests:
+ * no kernel handles it with naturally aligned accesses; DESIGN.md "Leading dimensions of the GEMMs").  fmmt_linear_fwd_seg3 holds
+ * ldy, and fmmt_linear_fwd_splitk N and ldy, to the same rule.
  */
 int fmmt_linear_fwd(int dtype, int M, int N, int K,
                     const void* x, int ldx, const void* w, int ldw, const float* bias,
@@ -104,7 +112,8 @@ int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void* x, int ld
  * x_epi = FMMT_EPI_GELU contracts with gelu(x) instead of x: the weight gradient of the second Linear of an Mlp whose
  * activation was not stored (fmmt_mlp_fwd keeps only the pre-activation); 0 = plain.
  * Query the workspace size first (it depends on dtype: the bf16 and fp32 kernels split the tokens differently).
- * N % 8 == 0 and K % 8 == 0 (bf16) / % 4 (f32). */
+ * N % 8 == 0 and K % 8 == 0 (bf16) / % 4 (f32); lddy >= N and ldx >= K, multiples of the same (dy and x may be views, as above; dw and db
+ * have no leading dimension: contiguous). */
 size_t fmmt_linear_wgrad_workspace(int dtype, int M, int N, int K);
 int fmmt_linear_wgrad(int dtype, int M, int N, int K,
                       const void* dy, int lddy, const void* x, int ldx,
@@ -541,6 +550,9 @@ int fmmt_eval_accumulate(int dtype, int B, int NL, const void* logits, int ld, c
  * pooling head with that loss behind its classifier (fmmt_pool_head_fwd_crit / _bwd_crit): likewise, held to _lib.LOSS_SIGNATURES.  Limits stated
  * there: den == 0 gives loss 0 and zero gradients (torch: NaN); the evaluation loss (fmmt_eval_accumulate) stays the plain cross-entropy. */
 #include "fmmt_loss.h"
+/* Which kernel family a GEMM launch takes, asked on the host through the dispatch itself (fmmt_linear_fwd_route, fmmt_linear_wgrad_route, enum fmmt_route):
+ * likewise, held to _lib.ROUTE_SIGNATURES. */
+#include "fmmt_route.h"
 
 #ifdef __cplusplus
 }

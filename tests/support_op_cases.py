@@ -36,6 +36,23 @@ def report(name, got, ref, tol):
     print(f"{'OK  ' if ok else 'FAIL'} {name:58s} max|err|={err:.3e} ref_scale={scale:.3e} tol={tol:g}", flush=True)
 
 
+def dropout_mean_bound(rows, p, rounding=0.0):
+    """6-sigma bound on |mean - 1| of attention outputs with v = 1 under dropout p on the probabilities.
+    Output row i (one query, batch element and head; the same in every channel of the head) is sum_j P_ij m_ij / (1 - p) with m_ij ~ Bernoulli(1 - p)
+    independent: expectation sum_j P_ij = 1, variance (p / (1 - p)) sum_j P_ij^2 <= p / (1 - p) whatever the probabilities are (sum_j P_ij^2 <= 1).
+    The mean over `rows` independent rows therefore has a standard error of at most sqrt(p / ((1 - p) rows)); `rounding` is the relative half-ulp of
+    the output type (the mean of values near 1 moves by no more than that)."""
+    return 6.0 * (p / ((1.0 - p) * rows)) ** 0.5 + rounding * 2.0
+
+
+def dropout_std_bounds(p, keys):
+    """(lower, upper) bound on the standard deviation of the same outputs: that dropout happened at all, and with the right scale.
+    Row i has variance (p / (1 - p)) sum_j P_ij^2, and 1 / keys <= sum_j P_ij^2 <= 1 (Cauchy-Schwarz; a one-hot row), so the expected variance of an
+    output lies in [p / ((1 - p) keys), p / (1 - p)].  The sample statistic over >= 1000 independent rows fluctuates by a few per cent; the bounds are
+    taken a factor 2 in the standard deviation outside that interval: a kernel that drops nothing gives std 0 (rounding apart), below the lower one."""
+    return 0.5 * (p / ((1.0 - p) * keys)) ** 0.5, 2.0 * (p / (1.0 - p)) ** 0.5
+
+
 def section(fn):
     try:
         fn()
@@ -491,7 +508,11 @@ def t_mha():
         o0 = ops.mha_core(q, k, v, 12, 0.125, 0.0, 0)
         report(f"mha v=1 p=0 {dt}", o0, torch.ones_like(o0), tol)
         o1 = ops.mha_core(q, k, v, 12, 0.125, 0.25, 1234)
-        print(f"     dropout p=0.25: mean(out)={o1.float().mean().item():.4f} (expect ~1), std={o1.float().std().item():.4f}")
+        mean, bound = o1.float().mean().item(), dropout_mean_bound(64 * 2 * 12, 0.25, 2.0 ** -9 if dt == torch.bfloat16 else 0.0)
+        std, (std_lo, std_hi) = o1.float().std().item(), dropout_std_bounds(0.25, 96)
+        ok = abs(mean - 1.0) <= bound and std_lo <= std <= std_hi and bool(torch.isfinite(o1.float()).all())
+        RES.append((f"mha v=1 p=0.25 kept mass {dt}", ok))
+        print(f"{'OK  ' if ok else 'FAIL'} mha dropout p=0.25 {dt}: mean(out)={mean:.4f} (1 +- {bound:.4f}), std={std:.4f} (in [{std_lo:.4f}, {std_hi:.4f}])", flush=True)
 
 
 def t_misc():
