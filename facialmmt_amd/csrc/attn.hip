@@ -16,6 +16,7 @@
 #include "wattn_args.h"
 #include "mha_args.h"
 #include <stdlib.h>
+#include <initializer_list>
 
 namespace {
 
@@ -575,6 +576,18 @@ int mha_check(int dtype, int Lq, int Lk, int B, int E, int nH) {
     return 0;
 }
 
+// The leading dimensions of the attention entry points (include/fmmt.h): every kernel, VALU (load_row / store_row -> ldvec: one 16-byte vector per
+// 8 bf16 / 4 fp32) and matrix-core alike, moves whole 16-byte vectors at row * ld + head * head_dim, so an ld that is not a multiple of 16 bytes
+// has no kernel: FMMT_EALIGN, as fmmt_mha_*_ragged.  An ld below E would overlap the rows: FMMT_EINVAL.
+int mha_ld_check(int dtype, int E, std::initializer_list<int> lds) {
+    const int per16 = dtype == FMMT_BF16 ? 8 : 4;
+    for (int ld : lds)
+        if (ld < E) return FMMT_EINVAL;
+    for (int ld : lds)
+        if (ld % per16) return FMMT_EALIGN;
+    return 0;
+}
+
 
 // Head-averaged (post-dropout) attention weights, multihead_attention.py:133-134: `attn_weights.view(bsz, heads, tgt, src).sum(1) / heads`.
 // No caller of the reference uses them (CrossmodalTransformer.py:147,151 discard them), so the attention kernels never form
@@ -766,6 +779,7 @@ extern "C" int fmmt_mha_avg_weights(int dtype, int Lq, int Lk, int B, int E, int
                                     const float* lse, float* weights, void* stream) {
     if (int e = mha_check(dtype, Lq, Lk, B, E, num_heads)) return e;
     if (!q || !k || !lse || !weights || dropout_p < 0.f || dropout_p >= 1.f) return FMMT_EINVAL;
+    if (int e = mha_ld_check(dtype, E, {ldq, ldkv})) return e;
     MhaArgs a{};
     a.Lq = Lq; a.Lk = Lk; a.B = B; a.E = E; a.nH = num_heads; a.q = q; a.ldq = ldq; a.k = k; a.ldkv = ldkv; a.scale = scale;
     a.key_bias = key_bias; a.drop_p = dropout_p; a.seed = seed; a.seed_dev = seed_dev; a.lse = const_cast<float*>(lse);
@@ -783,11 +797,13 @@ extern "C" int fmmt_mha_fwd(int dtype, int Lq, int Lk, int B, int E, int num_hea
     dtype &= ~FMMT_BATCH_MAJOR;
     if (int e = mha_check(dtype, Lq, Lk, B, E, num_heads)) return e;
     if (dropout_p < 0.f || dropout_p >= 1.f) return FMMT_EINVAL;
+    if (!q || !k || !v || !out || !lse) return FMMT_EINVAL;
+    if (int e = mha_ld_check(dtype, E, {ldq, ldkv, ldo})) return e;
     MhaArgs a{};
     a.Lq = Lq; a.Lk = Lk; a.B = B; a.E = E; a.nH = num_heads; a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldkv = ldkv;
     a.scale = scale; a.key_bias = key_bias; a.drop_p = dropout_p; a.seed = seed; a.seed_dev = seed_dev; a.out = out; a.ldo = ldo; a.lse = lse; a.bm = bm;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == FMMT_BF16 && E / num_heads == 64 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 8 == 0)
+    if (dtype == FMMT_BF16 && E / num_heads == 64)                   // (every ld is a multiple of 8 here: mha_ld_check)
         return fmmt_mha_mfma_fwd_launch(a, st);                      // matrix-core path
     FMMT_MHA_DISPATCH(K_FWD, (Lq + 63) / 64);
     return 0;
@@ -801,12 +817,14 @@ extern "C" int fmmt_mha_bwd(int dtype, int Lq, int Lk, int B, int E, int num_hea
     dtype &= ~FMMT_BATCH_MAJOR;
     if (int e = mha_check(dtype, Lq, Lk, B, E, num_heads)) return e;
     if (dropout_p < 0.f || dropout_p >= 1.f) return FMMT_EINVAL;
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv) return FMMT_EINVAL;
+    if (int e = mha_ld_check(dtype, E, {ldq, ldkv, ldo, lddq, lddkv})) return e;
     MhaArgs a{};
     a.Lq = Lq; a.Lk = Lk; a.B = B; a.E = E; a.nH = num_heads; a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldkv = ldkv;
     a.scale = scale; a.key_bias = key_bias; a.drop_p = dropout_p; a.seed = seed; a.seed_dev = seed_dev; a.out = const_cast<void*>(out); a.ldo = ldo;
     a.lse = const_cast<float*>(lse); a.dout = dout; a.dq = dq; a.lddq = lddq; a.dk = dk; a.dv = dv; a.lddkv = lddkv; a.bm = bm;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == FMMT_BF16 && E / num_heads == 64 && ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 8 == 0 && lddq % 8 == 0 && lddkv % 8 == 0)
+    if (dtype == FMMT_BF16 && E / num_heads == 64)                   // (every ld is a multiple of 8 here: mha_ld_check)
         return fmmt_mha_mfma_bwd_launch(a, st);                      // matrix-core path
     FMMT_MHA_DISPATCH(K_DQ, (Lq + 63) / 64);
     FMMT_MHA_DISPATCH(K_DV, (Lk + 63) / 64);

@@ -162,8 +162,8 @@ int fmmt_mlp_bwd_input(int dtype, int M, int C, const void* dy, const void* h_pr
 /* The same launch with the backward of the block's norm2 (Swin_Transformer.py:267-268: x = x + drop_path(mlp(norm2(x)))) as its tile
  * epilogue: instead of d(LN out) it writes dx = LayerNorm'(d(LN out); x, mean, rstd, gamma) + dy, the gradient of the block's residual
  * stream below the Mlp half, and d(gamma) / d(beta) of norm2 (per-workgroup partial sums in `workspace`, summed in fixed order by a
- * second small launch).  x: the LayerNorm's input (M, C); mean / rstd: the statistics fmmt_mlp_ln_fwd saved.  bf16, C = 96
- * (FMMT_EINVAL otherwise: fmmt_mlp_bwd_input + fmmt_layernorm_bwd).  Replaces autograd through nn.LayerNorm + Mlp. */
+ * second small launch).  x: the LayerNorm's input (M, C); mean / rstd: the statistics fmmt_mlp_ln_fwd saved.  C = 96 or 192
+ * (FMMT_EINVAL otherwise: fmmt_mlp_bwd_input + fmmt_layernorm_bwd); bf16, or FMMT_F32 / FMMT_GENERIC as the other fused Mlp entry points.  Replaces autograd through nn.LayerNorm + Mlp. */
 size_t fmmt_mlp_ln_bwd_input_workspace(int C);
 int fmmt_mlp_ln_bwd_input(int dtype, int M, int C, const void* dy, const void* h_pre, const void* w2t, const void* w1t,
                           const float* rowscale, int rows_per_scale, const void* x, const float* mean, const float* rstd,
@@ -305,6 +305,12 @@ int fmmt_window_block_attn_bwd_ref(int dtype, int n_img, int H, int W, int C, in
  * cross-modal encoder passes NULL (it has no key-padding mask at all); the per-modality self-attention encoders
  * (modules/Transformer.py:93-95 `attention_scores + attention_mask`, mask built at src/models.py:157,164 as
  * (1 - m) * -10000) pass their extended attention mask squeezed to [B, Lk].  No gradient is produced for it.
+ * Leading dimensions (the rules of fmmt_mha_fwd_ragged / _bwd_ragged, fmmt_tokens.h): ldq (q), ldkv (k, v), ldo (out AND dout), lddq (dq), lddkv (dk, dv)
+ * are independent row pitches in elements; each is >= E, else FMMT_EINVAL, and a multiple of 16 bytes (bf16: 8 elements, f32: 4), else FMMT_EALIGN --
+ * every kernel, VALU and matrix-core, moves 16-byte vectors at row * ld + head * head_dim, so no kernel serves another pitch (until the kernel-bounds
+ * tests a bf16 pitch off a multiple of 8 was quietly routed to the VALU kernels, which would have made those accesses at 8- or 2-byte alignment).
+ * q, k, v, out, lse -- and for the backward dout, dq, dk, dv; for fmmt_mha_avg_weights q, k, lse, weights -- are required: NULL is FMMT_EINVAL.
+ * key_bias and seed_dev may be NULL.  A refused call launches nothing.  Nothing outside the rows x E region of out / dq / dk / dv is written.
  */
 int fmmt_mha_fwd(int dtype, int Lq, int Lk, int B, int E, int num_heads,
                  const void* q, int ldq, const void* k, const void* v, int ldkv, float scale, const float* key_bias,
