@@ -31,7 +31,6 @@ update how many rows exist (ops.eval_accumulate_rows).  Several ranks: each eval
 all-gathers accumulators and rows and ops.eval_merge makes the one split of them on the device, in dataset order, the same on every rank."""
 from __future__ import annotations
 
-import contextlib
 import types
 
 import numpy as np
@@ -39,7 +38,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
-from .graph_capture import _KEEP_GRAPHS, capture_window, check_static_shapes, copy_into_static, distinct_stream, require_packet_capture_off, warmup_undone
+from .graph_capture import _KEEP_GRAPHS, _autocast, capture_window, check_static_shapes, copy_into_static, distinct_stream, require_packet_capture_off, warmup_undone
 from .train_step import _clamp_counts, _pin_shadows, check_frame_total, frame_buckets, fused_inference, pad_target_batch, pick_bucket, select_frames  # noqa: F401
 
 EMOTIONS = ("Neutral", "Surprise", "Fear", "Sadness", "Joy", "Disgust", "Anger")      # class order of eval_meld (utils/eval_metrics.py:27)
@@ -214,10 +213,6 @@ class _eval_mode:
         for m, t in self.was:
             m.training = t
         return False
-
-
-def _autocast(dtype):
-    return torch.autocast("cuda", dtype=dtype) if dtype is not None else contextlib.nullcontext()
 
 
 def _check_padded_frames(frames, vision_inputs):

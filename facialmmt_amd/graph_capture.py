@@ -17,6 +17,11 @@ def require_packet_capture_off(who):
                            "capture, gradients of replayed graphs are wrong from the third replay on")
 
 
+def _autocast(dtype, **kw):
+    """`with _autocast(dtype):` -- torch.autocast on the GPU at `dtype`, nothing at None (`kw`: torch.autocast's, e.g. cache_enabled=False)"""
+    return torch.autocast("cuda", dtype=dtype, **kw) if dtype is not None else contextlib.nullcontext()
+
+
 def pick_concurrent_stream(device, candidates: int = 8, cycles: int = 4_000_000):
     """A HIP stream that really runs concurrently with the current one.  HIP multiplexes streams onto a handful of
     hardware queues (4 by default) and two streams that share a queue serialise; which queue a new stream lands on

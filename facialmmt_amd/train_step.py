@@ -11,7 +11,7 @@ import types
 import torch
 import torch.nn.functional as F
 
-from .graph_capture import (_KEEP_GRAPHS, _bump_versions, _reset_optimizer_state, capture_window, copy_into_static,  # noqa: F401
+from .graph_capture import (_KEEP_GRAPHS, _autocast, _bump_versions, _reset_optimizer_state, capture_window, copy_into_static,  # noqa: F401
                             distinct_stream, pick_concurrent_stream, replay_update, require_packet_capture_off, warmup_undone)
 from . import step_state
 from .step_state import StepState
@@ -422,7 +422,6 @@ def graph_multimodal(mm, sample_args, autocast_dtype=None, overlap_text=True, pa
     visual path, and its small launches fill the CUs that Swin's large launches leave idle between waves
     (measured on an MI355X: text encoder 28.4 ms + Swin 52.9 ms = 82.8 ms back to back, 66.9 ms concurrently).
     Returns the module (its forward now replays the graphs)."""
-    import contextlib
     require_packet_capture_off("graph_multimodal")
     ids, attn_mask, sep_mask, audio, audio_mask, vision, vision_mask, utt_idx = sample_args
     utt_idx = torch.as_tensor(utt_idx, device=ids.device)
@@ -449,8 +448,7 @@ def graph_multimodal(mm, sample_args, autocast_dtype=None, overlap_text=True, pa
     # independent halves of the fusion stack (audio / vision encoder, the two directions of each cross-modal encoder) are
     # captured as parallel branches of the fusion graphs: models._pair
     mm.pair_stream = distinct_stream(ids.device, (side,)) if parallel_fusion else None
-    ctx = torch.autocast("cuda", dtype=autocast_dtype, cache_enabled=False) if autocast_dtype is not None else contextlib.nullcontext()
-    with ctx, capture_window():
+    with _autocast(autocast_dtype, cache_enabled=False), capture_window():
         gtext, gfusion = torch.cuda.make_graphed_callables(
             (text, fusion),
             ((ids, attn_mask, sep_mask, utt_idx), (text_feat, text_mask, audio, audio_mask, vision, vision_mask)),
@@ -600,12 +598,8 @@ class TargetStep(StepState):
         last = self.i_batch % args.trg_accumulation_steps == 0
         if getattr(self.mm, "text_stream", None) is not None:
             # start the text branch on its own stream before the Swin forward is enqueued (models.launch_text)
-            with _text_rows(self.mm, rows):
-                if self.autocast_dtype is not None:
-                    with torch.autocast("cuda", dtype=self.autocast_dtype):
-                        self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
-                else:
-                    self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
+            with _text_rows(self.mm, rows), _autocast(self.autocast_dtype):
+                self.mm.launch_text(ids, attn_mask, sep_mask, utt_idx)
         if self.color_jitter is not None:                   # one record per frame Swin runs on (packed: per slot of the capacity), drawn just ahead of Swin
             self.last_jitter = swin_kw["jitter"] = self.color_jitter.draw(frames.shape[0], frames.device)
         if self.skip_swin_bwd:
@@ -619,12 +613,8 @@ class TargetStep(StepState):
         # gradient exchange only on the last micro-step of the window; torch's DDP decides in its FORWARD whether the
         # coming backward synchronises, so the no_sync context has to cover the forward as well
         with accumulate(self.exchange, last):
-            with _text_rows(self.mm, rows):
-                if self.autocast_dtype is not None:
-                    with torch.autocast("cuda", dtype=self.autocast_dtype):
-                        logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
-                else:
-                    logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
+            with _text_rows(self.mm, rows), _autocast(self.autocast_dtype):
+                logits = self.mm_call(ids, attn_mask, sep_mask, audio, audio_mask, vis_concat, new_mask, utt_idx)
             mark("multimodal_fwd")
             loss = _loss_of(self.criterion, logits, labels) / args.trg_accumulation_steps
             loss.backward()
@@ -1794,6 +1784,12 @@ class FlatGradientTail:
             l.grad = None
 
 
+def _default_mode_only(argument):
+    """what GraphedTargetStep answers to `argument` (token_capacity, pad_rows, frame_capacity) together with one of its three side modes"""
+    raise NotImplementedError(f"{argument}: the default single-graph mode, or the two-piece mode of an active gradient exchange (not with "
+                              "pipeline_swin / branch_graphs / fork_streams)")
+
+
 class GraphedTargetStep(StepState):
     """The whole target-task step as HIP graphs, replayed per step with one host call each -- two graphs (A = A1 + A2 as one, then B) on
     a single GPU, three when a gradient exchange has to be hidden (N > 1):
@@ -1906,25 +1902,23 @@ class GraphedTargetStep(StepState):
         if self.token_capacity < 0:
             raise ValueError("token_capacity: a number of rows, 0 (padded layout) or None (from the sample batch)")
         if self.token_capacity and other_mode:
-            raise NotImplementedError("token_capacity: the default single-graph mode, or the two-piece mode of an active gradient exchange (not with "
-                                      "pipeline_swin / branch_graphs / fork_streams)")
+            _default_mode_only("token_capacity")
         if self.token_capacity and not token_fit(batch[1], self.token_capacity):      # ValueError: the sample itself does not fit
             raise ValueError("token_capacity: the sample batch's text mask has a hole; the captures need a sample that packs")
-        self.token_replays, self._padded_graphs = {"packed": 0, "padded": 0}, {}
+        self.token_replays = {"packed": 0, "padded": 0}
         self.twin_capture_bytes, self.twin_capture_reserved_bytes = {}, {}
         self._rows_now = self.token_capacity                # what the pass in progress (warm-up, capture) runs the text branch with: _text_rows sets it on
                                                             # the model for the length of that forward only, so nobody else who calls the model ever packs
         self.criterion = _check_criterion(criterion, getattr(args, "num_labels", None))
         self.skip_swin_bwd = discarded_swin_gradients == "skip"
         self.pipeline = bool(pipeline_swin)
-        self.branches = bool(branch_graphs)                 # BRANCH_NOTE below
+        self.branches = bool(branch_graphs)                 # BRANCH_NOTE at _capture_branches
         self.forked = bool(fork_streams)                    # FORK_NOTE at _fwd_bwd_forked
         self.pad_rows, self.rows, self.padded_calls = bool(pad_rows), None, 0
         if self.pad_rows and frame_capacity is None:
             raise ValueError("pad_rows: only with frame_capacity (compact frames change their shape with the batch's rows)")
-        if self.pad_rows and (pipeline_swin or branch_graphs or fork_streams):
-            raise NotImplementedError("pad_rows: the default single-graph mode, or the two-piece mode of an active gradient exchange (not with "
-                                      "pipeline_swin / branch_graphs / fork_streams)")
+        if self.pad_rows and other_mode:
+            _default_mode_only("pad_rows")
         if (self.pad_rows or frame_capacity is not None) and bool(getattr(averager, "active", False)) and not isinstance(averager, GradientAverager):
             # the per-capacity pairs and the row weight are built on GradientAverager: its flat buffers are what the capacities share, its
             # world size is what weights the rows.  Another object that calls itself active is an exchange this step has no path for.
@@ -1935,9 +1929,8 @@ class GraphedTargetStep(StepState):
         self.capacity, self.replays, self.capture_bytes, self.capture_reserved_bytes = None, {c: 0 for c in self.capacities or ()}, {}, {}
         self._cap = self.frame_capacity                     # the capacity the pass in progress (warm-up, capture) packs into
         if self.frame_capacity is not None:
-            if self.pipeline or self.branches or self.forked:
-                raise NotImplementedError("frame_capacity: the default single-graph mode, or the two-piece mode of an active gradient exchange (not "
-                                          "with pipeline_swin / branch_graphs / fork_streams)")
+            if other_mode:
+                _default_mode_only("frame_capacity")
             if batch[8].dim() < 3:
                 raise ValueError("frame_capacity: a positive number of frames, and `frames` as the loader pads them, (B, Lv, ...)")
             check_frame_total(batch[9], batch[8].shape[1], self.frame_capacity)
@@ -1983,6 +1976,19 @@ class GraphedTargetStep(StepState):
                 self.text_stream = distinct_stream(dev, (cap,))
             self.swin_stream = distinct_stream(dev, tuple(x for x in (cap, self.text_stream, self.mm.pair_stream) if x is not None))
             self._tick = torch.zeros(1, device=dev)
+        # With an exchange to hide (N > 1) the forward/backward is TWO graphs, cut where the multimodal gradients are complete; alone on
+        # the GPU it stays ONE graph: inside it the text encoder's backward runs as a branch beside Swin's backward, which a cut in
+        # front of Swin's backward would serialise (measured at N = 1: 72.1 ms per step cut, 69 ms uncut).
+        self.split = bool(getattr(self.flat, "active", False))
+        if swin_cut not in (0, 1, 2):
+            raise ValueError("swin_cut: 0, 1 or 2")
+        self.SWIN_CUT = int(swin_cut)                      # the window behind the cut has to hold the exchange: see pick_swin_cut
+        if self.pipeline and (self.split or self.skip_swin_bwd):
+            raise ValueError("pipeline_swin: one rank without a gradient exchange, Swin's backward computed")
+        if self.branches and (self.split or self.skip_swin_bwd or self.pipeline):
+            raise ValueError("branch_graphs: one rank without a gradient exchange, Swin's backward computed, not together with pipeline_swin")
+        if self.forked and (self.split or self.skip_swin_bwd or self.pipeline or self.branches):
+            raise ValueError("fork_streams: one rank without a gradient exchange, Swin's backward computed, not together with pipeline_swin / branch_graphs")
         # -- warm-up on a side stream (lazy initialisations: kernel attributes, shadow caches, optimizer state), undone below
         snap = [(t, t.detach().clone()) for m in (self.swin, self.mm) for t in list(m.parameters()) + list(m.buffers())]
         if masters is not None:
@@ -2013,167 +2019,77 @@ class GraphedTargetStep(StepState):
         self.shadows = _pin_shadows([self.swin, self.mm])
         self.swin_shadows = self.mm_shadows = None
         self._swin_params = [q for q in self.swin.parameters()]
-        # With an exchange to hide (N > 1) the forward/backward is TWO graphs, cut where the multimodal gradients are complete; alone on
-        # the GPU it stays ONE graph: inside it the text encoder's backward runs as a branch beside Swin's backward, which a cut in
-        # front of Swin's backward would serialise (measured at N = 1: 72.1 ms per step cut, 69 ms uncut).
-        self.split = bool(getattr(self.flat, "active", False))
-        if swin_cut not in (0, 1, 2):
-            raise ValueError("swin_cut: 0, 1 or 2")
-        self.SWIN_CUT = int(swin_cut)                      # the window behind the cut has to hold the exchange: see pick_swin_cut
-        if self.pipeline and (self.split or self.skip_swin_bwd):
-            raise ValueError("pipeline_swin: one rank without a gradient exchange, Swin's backward computed")
-        if self.branches and (self.split or self.skip_swin_bwd or self.pipeline):
-            raise ValueError("branch_graphs: one rank without a gradient exchange, Swin's backward computed, not together with pipeline_swin")
-        if self.forked and (self.split or self.skip_swin_bwd or self.pipeline or self.branches):
-            raise ValueError("fork_streams: one rank without a gradient exchange, Swin's backward computed, not together with pipeline_swin / branch_graphs")
         self.graph_a, self.graph_a2, self.graph_b = torch.cuda.CUDAGraph(), (torch.cuda.CUDAGraph() if self.split else None), torch.cuda.CUDAGraph()
         self.sets, self.side_stream, self.cur, self.prefetched = [], None, 0, None
-        self._graphs = {}                                   # several capacities: capacity -> (graph A, its loss, its kept-frame mask)
-        self._graphs_a2 = {}                                # ... under an exchange: capacity -> graph A2 (graph A above is A1)
+        # the default mode's forward/backward captures, the ONE table __call__ looks a batch's up in: (frame capacity -- None without one --,
+        # packed) -> a1, a2 (None unless split), loss, mask.  packed=True: the capture on packed token rows, and the only one with token_capacity
+        # == 0; packed=False: its padded twin.  graph_a / graph_a2 / loss / new_mask are the sample batch's own record: largest capacity, packed
+        self._captures = {}
         if self.pipeline:
-            # two sets (graph S: Swin forward; graph A': everything else), each in a memory pool of ITS OWN: S of one set replays beside A' of the
-            # other, and inside a shared pool the capture of the second set would reuse blocks the first set's backward freed
-            self.side_stream = distinct_stream(dev, tuple(x for x in (cap, self.text_stream, self.mm.pair_stream) if x is not None))
-            self.swin_shadows, self.mm_shadows = _pin_shadows([self.swin]), _pin_shadows([self.mm])
-            with capture_window(), ops.pinned_scope(self.shadows):
-                for k in range(2):
-                    frames_k = self.static[8] if k == 0 else self.static[8].clone()
-                    g_s, g_a = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g_s, stream=cap):
-                        preds = self._swin_forward(frames_k)
-                    with torch.cuda.graph(g_a, pool=g_s.pool(), stream=cap):
-                        loss, new_mask, _ = self._fwd_bwd_multimodal(whole=True, preds=preds)
-                    del preds
-                    self.sets.append(types.SimpleNamespace(S=g_s, A=g_a, frames=frames_k, loss=loss, mask=new_mask,
-                                                           ev_s=torch.cuda.Event(), ev_a=torch.cuda.Event()))
-                    _KEEP_GRAPHS.append((g_s, g_a))
-                with torch.cuda.graph(self.graph_b, stream=cap):
-                    tail.update()
-            self.loss, self.new_mask = self.sets[0].loss, self.sets[0].mask
+            self._capture_pipelined(cap)
         elif self.branches:
-            # BRANCH_NOTE.  Inside ONE graph the text encoder and Swin are two branches, but the replay does not run them side by side: the
-            # runtime enqueues a graph branch by branch, and a branch that continues on another queue waits for EVERYTHING the first branch
-            # has enqueued so far, not for the node it depends on (profiles/r05_timeline.txt: the text encoder's forward runs alone for
-            # ~4 ms in front of Swin's forward -- behind it when the capture order is swapped, TEXT_FORK_AT --, its backward starts ~12 ms
-            # into Swin's backward and ends ~5 ms after it).  Here every branch is a graph of its own, launched on one of two streams with
-            # events between them -- dependencies exactly where the data flow has them:
-            #     side:  T  text encoder forward ............................ TB text encoder backward, hand-over | B update
-            #     main:  S  Swin forward -> [T] F  frame filter, fusion stack, loss, its backward -> SB Swin backward
-            # Autograd crosses the graph boundaries on detached copies of the two branch outputs (F differentiates down to them, TB / SB
-            # continue from their gradients).  Pools: graphs that may run at the same time never share one (T, TB, B | S, SB | F).
-            self.side_stream = distinct_stream(dev, (cap,))
-            self.swin_shadows, self.mm_shadows = _pin_shadows([self.swin]), _pin_shadows([self.mm])
-            g = types.SimpleNamespace(T=torch.cuda.CUDAGraph(), S=torch.cuda.CUDAGraph(), F=torch.cuda.CUDAGraph(), TB=torch.cuda.CUDAGraph(),
-                                      SB=torch.cuda.CUDAGraph(), ev_t=torch.cuda.Event(), ev_f=torch.cuda.Event())
-            with capture_window(), ops.pinned_scope(self.shadows):
-                with torch.cuda.graph(g.T, stream=cap):
-                    feat, tmask = self._text_forward()
-                with torch.cuda.graph(g.S, stream=cap):
-                    preds = self._swin_forward(self.static[8])
-                with torch.cuda.graph(g.F, stream=cap):
-                    self.loss, self.new_mask, dfeat, dpreds = self._fusion_fwd_bwd(feat, tmask, preds)
-                with torch.cuda.graph(g.TB, pool=g.T.pool(), stream=cap):
-                    self._text_backward(feat, dfeat)
-                with torch.cuda.graph(g.SB, pool=g.S.pool(), stream=cap):
-                    self._bwd_swin((preds, dpreds))
-                del feat, tmask, preds, dfeat, dpreds
-                with torch.cuda.graph(self.graph_b, pool=g.T.pool(), stream=cap):
-                    tail.update()
-            self.bg = g
-            _KEEP_GRAPHS.append((g.T, g.S, g.F, g.TB, g.SB))
+            self._capture_branches(cap)
         else:
-          with capture_window(), ops.pinned_scope(self.shadows):
-            if self.split:
-                # One pair (A1_c, A2_c) per capacity c (a compact step or frame_capacity=int: the one pair), A2_c in A1_c's pool -- it continues from
-                # the activations A1_c saved -- and every pair in a pool of its own: BUCKET_NOTE below, unchanged.  The exchange between the two
-                # only sees the flat buffers, which no capacity sizes: ranks may replay different capacities in the same step.
-                for c in self.capacities or (None,):
-                    if multi:
-                        self._use_capacity(c, batch)
-                    own = not multi or c == self.capacities[-1]
-                    g1, g2 = (self.graph_a, self.graph_a2) if own else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph())
-                    before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
-                    with torch.cuda.graph(g1, stream=cap):
-                        loss, new_mask, swin_out = self._fwd_bwd_multimodal()
-                    with torch.cuda.graph(g2, pool=g1.pool(), stream=cap):
-                        self._bwd_swin(swin_out)
-                    del swin_out
-                    if c is not None:
-                        self.capture_bytes[c] = torch.cuda.memory_allocated(dev) - before[0]
-                        self.capture_reserved_bytes[c] = torch.cuda.memory_reserved(dev) - before[1]
-                    if multi:
-                        self._graphs[c], self._graphs_a2[c] = (g1, loss, new_mask), g2
-                        _KEEP_GRAPHS.append((g1, g2))
-                        # as on the single-graph bucket path: no Swin gradient survives into the next pair's capture -- here that includes the
-                        # parameters above the cut, whose .grad A1 assigns (`late` in _fwd_bwd_multimodal)
-                        self.swin.zero_grad(set_to_none=True)
-                self.loss, self.new_mask = loss, new_mask
-                if multi:
-                    with torch.cuda.graph(self.graph_b, stream=cap):
-                        tail.update()
-            elif multi:
-                # BUCKET_NOTE.  One graph A per capacity, each in a memory pool of ITS OWN: a graph keeps its saved activations in its pool between
-                # its forward and its backward, and graphs that replay in an order the batches decide must not hand each other's blocks out.
-                # Shared, because every capture addresses the same objects: the static inputs, the flat gradient buffers and the hand-over's
-                # destinations, the shadows, the generator, the counts word -- and graph B, which reads none of a graph A's pool (the gradients
-                # have left it through the hand-over) and therefore runs behind whichever A ran; it gets a pool of its own as well
-                for c in self.capacities:
-                    self._use_capacity(c, batch)
-                    g = self.graph_a if c == self.capacities[-1] else torch.cuda.CUDAGraph()
-                    before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
-                    with torch.cuda.graph(g, stream=cap):
-                        loss, new_mask = self._fwd_bwd()
-                    self.capture_bytes[c] = torch.cuda.memory_allocated(dev) - before[0]
-                    self.capture_reserved_bytes[c] = torch.cuda.memory_reserved(dev) - before[1]
-                    self._graphs[c] = (g, loss, new_mask)
-                    _KEEP_GRAPHS.append((g,))
-                    # every capture starts, as the single one does, without Swin gradients: left in place, the next capture's backward would ADD
-                    # into them -- ~170 more launches per replay, writing into this capture's pool
-                    self.swin.zero_grad(set_to_none=True)
-                self.loss, self.new_mask = loss, new_mask
-                with torch.cuda.graph(self.graph_b, stream=cap):
+            caps = self.capacities or (None,)
+            with capture_window(), ops.pinned_scope(self.shadows):
+                for c in caps:
+                    own = (self.graph_a, self.graph_a2) if c == caps[-1] else None
+                    self._captures[c, True] = self._capture(c, True, batch, cap, own)
+                # graph B reads none of a graph A's pool (the gradients have left it through the hand-over) and therefore runs behind whichever A
+                # ran: with several capacities it gets a pool of its own as well (BUCKET_NOTE), with one it shares graph A's
+                with torch.cuda.graph(self.graph_b, pool=None if multi else self.graph_a.pool(), stream=cap):
                     tail.update()
-            else:
-                before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
-                with torch.cuda.graph(self.graph_a, stream=cap):
-                    self.loss, self.new_mask = self._fwd_bwd()
-                if self.frame_capacity is not None:
-                    self.capture_bytes[self.frame_capacity] = torch.cuda.memory_allocated(dev) - before[0]
-                    self.capture_reserved_bytes[self.frame_capacity] = torch.cuda.memory_reserved(dev) - before[1]
-            if not multi:
-                with torch.cuda.graph(self.graph_b, pool=self.graph_a.pool(), stream=cap):
-                    tail.update()
-            if self.token_capacity:
-                # the padded twins (token_capacity above): per frame capacity the same forward/backward with the text encoder on the padded layout,
-                # in a pool of its own for the reason of BUCKET_NOTE; no Swin gradient of an earlier capture may be left to add into
-                self._rows_now = 0
-                for c in self.capacities or (None,):
-                    if multi:
-                        self._use_capacity(c, batch)
-                    self.swin.zero_grad(set_to_none=True)
-                    g1, g2 = torch.cuda.CUDAGraph(), (torch.cuda.CUDAGraph() if self.split else None)
-                    before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
-                    if self.split:
-                        with torch.cuda.graph(g1, stream=cap):
-                            loss, new_mask, swin_out = self._fwd_bwd_multimodal()
-                        with torch.cuda.graph(g2, pool=g1.pool(), stream=cap):
-                            self._bwd_swin(swin_out)
-                        del swin_out
-                    else:
-                        with torch.cuda.graph(g1, stream=cap):
-                            loss, new_mask = self._fwd_bwd()
-                    self._padded_graphs[c if multi else None] = (g1, loss, new_mask, g2)
-                    self.twin_capture_bytes[c] = torch.cuda.memory_allocated(dev) - before[0]
-                    self.twin_capture_reserved_bytes[c] = torch.cuda.memory_reserved(dev) - before[1]
-                    _KEEP_GRAPHS.append((g1, g2))
-                self._rows_now = self.token_capacity
+                if self.token_capacity:
+                    # the padded twins (token_capacity above): per frame capacity the same forward/backward with the text encoder on the padded layout
+                    for c in caps:
+                        self._captures[c, False] = self._capture(c, False, batch, cap)
+            self.loss, self.new_mask = self._captures[caps[-1], True].loss, self._captures[caps[-1], True].mask
         _KEEP_GRAPHS.append((self.graph_a, self.graph_a2, self.graph_b))
-        self._own_outputs = (self.loss, self.new_mask)     # the packed (or only) capture's outputs: a call of a padded twin swaps its own in
         if multi:
             self._use_capacity(self.capacities[-1], batch)  # the sample's own counts (they fit the largest capacity) back in the static input
         self.swin.zero_grad(set_to_none=True)              # drop the references; the graph's pool keeps the buffers
         self.mm.pair_stream = None
         self.flat.zero_grad()                              # the capture itself executes nothing
+
+    def _capture(self, c, packed, batch, cap, graphs=None):
+        """ONE forward/backward capture of the default mode, on stream `cap`: into frame capacity `c` (None: the step has none), with the text branch on
+        packed token rows or (`packed` False: a padded twin) on the padded layout; into `graphs` = (A1, A2) -- the constructor's graph_a / graph_a2 for
+        the sample batch's own capture -- or fresh ones.  Returns the record of `_captures`; the byte deltas go to capture_bytes / twin_capture_bytes
+        (and their reserved twins) under `c`.
+        Alone on the GPU the forward/backward is one graph (_fwd_bwd).  Split (an active exchange): a PAIR (A1, A2), A2 in A1's pool -- it continues
+        from the activations A1 saved; the exchange between the two only sees the flat buffers, which no capacity sizes: ranks may replay different
+        capacities in the same step.
+        BUCKET_NOTE.  Every capture but the sample's own single one gets a memory pool of ITS OWN: a graph keeps its saved activations in its pool
+        between its forward and its backward, and graphs that replay in an order the batches decide must not hand each other's blocks out.  Shared,
+        because every capture addresses the same objects: the static inputs, the flat gradient buffers and the hand-over's destinations, the
+        shadows, the generator, the counts word -- and graph B."""
+        dev = self.static[0].device
+        if self._counts_buf is not None:                    # several capacities: pack into `c`, on the sample's counts cut down to fit it
+            self._use_capacity(c, batch)
+        # every capture starts, as the first does, without Swin gradients: left in place, this capture's backward would ADD into an earlier one's --
+        # ~170 more launches per replay, writing into that capture's pool.  Split, that includes the parameters above the cut, whose .grad A1
+        # assigns (`late` in _fwd_bwd_multimodal)
+        self.swin.zero_grad(set_to_none=True)
+        self._rows_now = self.token_capacity if packed else 0
+        a1, a2 = graphs if graphs is not None else (torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph() if self.split else None)
+        before = (torch.cuda.memory_allocated(dev), torch.cuda.memory_reserved(dev))
+        if self.split:
+            with torch.cuda.graph(a1, stream=cap):
+                loss, new_mask, swin_out = self._fwd_bwd_multimodal()
+            with torch.cuda.graph(a2, pool=a1.pool(), stream=cap):
+                self._bwd_swin(swin_out)
+            del swin_out
+        else:
+            with torch.cuda.graph(a1, stream=cap):
+                loss, new_mask = self._fwd_bwd()
+        grew = (torch.cuda.memory_allocated(dev) - before[0], torch.cuda.memory_reserved(dev) - before[1])
+        if not packed:                                      # a twin is recorded under None as well: a step without a frame capacity has one too
+            self.twin_capture_bytes[c], self.twin_capture_reserved_bytes[c] = grew
+        elif c is not None:
+            self.capture_bytes[c], self.capture_reserved_bytes[c] = grew
+        self._rows_now = self.token_capacity
+        _KEEP_GRAPHS.append((a1, a2))
+        return types.SimpleNamespace(a1=a1, a2=a2, loss=loss, mask=new_mask)
 
     # one micro-step: forward + backward (runs eagerly during warm-up, once more under capture), in the two pieces the graphs hold
     def _fwd_bwd(self):
@@ -2231,21 +2147,17 @@ class GraphedTargetStep(StepState):
         (ids, attn_mask, sep_mask, _a, _am, _v, _vm, _l, _f, _n, utt_idx) = self.static
         if refresh and self.mm_shadows is not None:
             self.mm_shadows.refresh()
-        import contextlib
-        ac = (lambda: torch.autocast("cuda", dtype=self.autocast_dtype)) if self.autocast_dtype is not None else contextlib.nullcontext
-        with ac(), _text_rows(self.mm, self._rows_now):
+        with _autocast(self.autocast_dtype), _text_rows(self.mm, self._rows_now):
             return self.mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
 
     def _fusion_fwd_bwd(self, feat, tmask, preds):
         """branch_graphs, graph F: frame filter, fusion stack, loss and their backward, down to detached copies of the two branch outputs;
         returns (loss, kept-frame mask, d(text features), d(Swin output)).  The fusion stack's parameter gradients are complete here."""
         (_i, _m, _s, audio, audio_mask, vision_inputs, vision_mask, labels, _f, num_imgs, _u) = self.static
-        import contextlib
-        ac = (lambda: torch.autocast("cuda", dtype=self.autocast_dtype)) if self.autocast_dtype is not None else contextlib.nullcontext
         feat_d = feat.detach().requires_grad_(True)
         preds_d = preds.detach().requires_grad_(True)
         vis_concat, new_mask = select_frames(preds_d.float(), vision_inputs, vision_mask, num_imgs, self.args.FacialEmoImpor_threshold)
-        with ac():
+        with _autocast(self.autocast_dtype):
             logits = self.mm.fusion_branch(feat_d, tmask, audio, audio_mask, vis_concat, new_mask)
         loss = _loss_of(self.criterion, logits, labels) / self.args.trg_accumulation_steps
         leaves = [l for l, _ in self.pairs if l.requires_grad]
@@ -2266,6 +2178,43 @@ class GraphedTargetStep(StepState):
                     l.grad = gr if l.grad is None else l.grad + gr      # (a parameter both pieces use: none in this model)
         if handover:
             self.tail.hand_over()
+
+    # branch_graphs and fork_streams are measured and not adopted (BRANCH_NOTE, FORK_NOTE).  They stay: bench.py passes both keywords on every
+    # construction, and tests/test_gpu_train_step.py holds them to the in-order trajectory.
+    def _capture_branches(self, cap):
+        """branch_graphs: the constructor's captures on stream `cap` (_call_branches replays them)"""
+        from . import ops
+        dev, tail = self.static[0].device, self.tail
+        # BRANCH_NOTE.  Inside ONE graph the text encoder and Swin are two branches, but the replay does not run them side by side: the
+        # runtime enqueues a graph branch by branch, and a branch that continues on another queue waits for EVERYTHING the first branch
+        # has enqueued so far, not for the node it depends on (profiles/r05_timeline.txt: the text encoder's forward runs alone for
+        # ~4 ms in front of Swin's forward -- behind it when the capture order is swapped, TEXT_FORK_AT --, its backward starts ~12 ms
+        # into Swin's backward and ends ~5 ms after it).  Here every branch is a graph of its own, launched on one of two streams with
+        # events between them -- dependencies exactly where the data flow has them:
+        #     side:  T  text encoder forward ............................ TB text encoder backward, hand-over | B update
+        #     main:  S  Swin forward -> [T] F  frame filter, fusion stack, loss, its backward -> SB Swin backward
+        # Autograd crosses the graph boundaries on detached copies of the two branch outputs (F differentiates down to them, TB / SB
+        # continue from their gradients).  Pools: graphs that may run at the same time never share one (T, TB, B | S, SB | F).
+        self.side_stream = distinct_stream(dev, (cap,))
+        self.swin_shadows, self.mm_shadows = _pin_shadows([self.swin]), _pin_shadows([self.mm])
+        g = types.SimpleNamespace(T=torch.cuda.CUDAGraph(), S=torch.cuda.CUDAGraph(), F=torch.cuda.CUDAGraph(), TB=torch.cuda.CUDAGraph(),
+                                  SB=torch.cuda.CUDAGraph(), ev_t=torch.cuda.Event(), ev_f=torch.cuda.Event())
+        with capture_window(), ops.pinned_scope(self.shadows):
+            with torch.cuda.graph(g.T, stream=cap):
+                feat, tmask = self._text_forward()
+            with torch.cuda.graph(g.S, stream=cap):
+                preds = self._swin_forward(self.static[8])
+            with torch.cuda.graph(g.F, stream=cap):
+                self.loss, self.new_mask, dfeat, dpreds = self._fusion_fwd_bwd(feat, tmask, preds)
+            with torch.cuda.graph(g.TB, pool=g.T.pool(), stream=cap):
+                self._text_backward(feat, dfeat)
+            with torch.cuda.graph(g.SB, pool=g.S.pool(), stream=cap):
+                self._bwd_swin((preds, dpreds))
+            del feat, tmask, preds, dfeat, dpreds
+            with torch.cuda.graph(self.graph_b, pool=g.T.pool(), stream=cap):
+                tail.update()
+        self.bg = g
+        _KEEP_GRAPHS.append((g.T, g.S, g.F, g.TB, g.SB))
 
     def _call_branches(self, batch):
         g, main, side = self.bg, torch.cuda.current_stream(), self.side_stream
@@ -2340,9 +2289,6 @@ class GraphedTargetStep(StepState):
         output comes from graph S; this piece starts behind it and its backward runs through S's autograd graph."""
         (ids, attn_mask, sep_mask, audio, audio_mask, vision_inputs, vision_mask, labels, frames, num_imgs, utt_idx) = self.static
         mm, args = self.mm, self.args
-        ctx = (lambda: torch.autocast("cuda", dtype=self.autocast_dtype)) if self.autocast_dtype is not None else None
-        import contextlib
-        ac = ctx if ctx is not None else contextlib.nullcontext
         main = torch.cuda.current_stream()
         pending = None
         if preds is not None:
@@ -2360,7 +2306,7 @@ class GraphedTargetStep(StepState):
 
             def launch_text(*_):
                 self.text_stream.wait_event(fork_ev)
-                with torch.cuda.stream(self.text_stream), ac(), _text_rows(mm, self._rows_now):
+                with torch.cuda.stream(self.text_stream), _autocast(self.autocast_dtype), _text_rows(mm, self._rows_now):
                     box["out"] = mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
 
             where = self.TEXT_FORK_AT if preds is None and not self.skip_swin_bwd else "start"
@@ -2400,7 +2346,7 @@ class GraphedTargetStep(StepState):
                 pending = box["out"]
         vis_concat, new_mask = select_frames(preds.float(), vision_inputs, vision_mask, num_imgs, args.FacialEmoImpor_threshold,
                                              self.frame_counts if self.frame_capacity is not None else None)
-        with ac():
+        with _autocast(self.autocast_dtype):
             if pending is None:
                 with _text_rows(mm, self._rows_now):
                     pending = mm.text_branch(ids, attn_mask, sep_mask, torch.as_tensor(utt_idx, device=ids.device))
@@ -2481,6 +2427,30 @@ class GraphedTargetStep(StepState):
             st.S.replay()
             st.ev_s.record(side)
 
+    def _capture_pipelined(self, cap):
+        """pipeline_swin: the constructor's captures on stream `cap` (_call_pipelined replays them)"""
+        from . import ops
+        dev, tail = self.static[0].device, self.tail
+        # two sets (graph S: Swin forward; graph A': everything else), each in a memory pool of ITS OWN: S of one set replays beside A' of the
+        # other, and inside a shared pool the capture of the second set would reuse blocks the first set's backward freed
+        self.side_stream = distinct_stream(dev, tuple(x for x in (cap, self.text_stream, self.mm.pair_stream) if x is not None))
+        self.swin_shadows, self.mm_shadows = _pin_shadows([self.swin]), _pin_shadows([self.mm])
+        with capture_window(), ops.pinned_scope(self.shadows):
+            for k in range(2):
+                frames_k = self.static[8] if k == 0 else self.static[8].clone()
+                g_s, g_a = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g_s, stream=cap):
+                    preds = self._swin_forward(frames_k)
+                with torch.cuda.graph(g_a, pool=g_s.pool(), stream=cap):
+                    loss, new_mask, _ = self._fwd_bwd_multimodal(whole=True, preds=preds)
+                del preds
+                self.sets.append(types.SimpleNamespace(S=g_s, A=g_a, frames=frames_k, loss=loss, mask=new_mask,
+                                                       ev_s=torch.cuda.Event(), ev_a=torch.cuda.Event()))
+                _KEEP_GRAPHS.append((g_s, g_a))
+            with torch.cuda.graph(self.graph_b, stream=cap):
+                tail.update()
+        self.loss, self.new_mask = self.sets[0].loss, self.sets[0].mask
+
     def _call_pipelined(self, batch, next_batch):
         k, st = self.cur, self.sets[self.cur]
         copy_into_static(self.static, batch, "GraphedTargetStep", skip=(8,))      # the frames belong to graph S (_launch_swin)
@@ -2522,42 +2492,32 @@ class GraphedTargetStep(StepState):
         weight = _check_global_rows("GraphedTargetStep", global_rows, self.row_weight, b, self.flat.world, rows)     # ValueError first of all
         if self.pad_rows and b != rows:
             batch = pad_target_batch(batch, rows)           # ValueError for b == 0 or b > rows, before any copy or launch
-        graph_a, graph_a2 = self.graph_a, self.graph_a2
         packed = token_fit(batch[1], self.token_capacity)   # ValueError before any copy or launch; False: padding off, or a mask with a hole
         c = None
         if self.capacities is not None:
             # the smallest capacity that holds the batch (host counts; a device tensor: the largest, unread); ValueError before any copy or launch
             c = frame_bucket(batch[9], self.static[8].shape[1], self.capacities)
-            if self._graphs:
-                graph_a, graph_a2 = self._graphs[c][0], self._graphs_a2.get(c)
-        twin = self._padded_graphs[c if self._graphs else None] if (self.token_capacity and not packed) else None     # keyed as _graphs is
-        if twin is not None:
-            graph_a, graph_a2 = twin[0], twin[3]
+        rec = self._captures[c, packed or not self.token_capacity]      # padding off: the only capture per capacity is filed as the packed one
         copy_into_static(self.static, batch, "GraphedTargetStep")
         if self.row_weight is not None:
             self.row_weight.fill_(weight)                   # a device fill: no host synchronisation
-        graph_a.replay()
+        rec.a1.replay()
+        self.loss, self.new_mask = rec.loss, rec.mask       # every capture has its own outputs
         self.rows = b
         self.padded_calls += int(b != rows)
         if self.capacities is not None:
             self.capacity = c
             self.replays[c] += 1
-            if self._graphs:
-                _, self.loss, self.new_mask = self._graphs[c]   # every graph A has its own outputs
         if self.token_capacity:
             self.token_replays["packed" if packed else "padded"] += 1
-            if twin is not None:
-                self.loss, self.new_mask = twin[1], twin[2]
-            elif not self._graphs:
-                self.loss, self.new_mask = self._own_outputs
         self.i_batch += 1
         last = self.i_batch % self.args.trg_accumulation_steps == 0
         if last:
             self.flat.exchange_begin()                     # no-op at world size 1; the collectives run beside graph A2
             if self.timing is not None:
                 self.timing["begin"].record()
-        if graph_a2 is not None:
-            graph_a2.replay()
+        if rec.a2 is not None:
+            rec.a2.replay()
         if last:
             if self.timing is not None:
                 self.timing["a2_done"].record()
@@ -2890,10 +2850,7 @@ class GraphedUnimodalStep(StepState):
         if self.criterion is not None:
             kw["criterion"] = self.criterion
         feature, mask, labels = self.static
-        if self.autocast_dtype is not None:
-            with torch.autocast("cuda", dtype=self.autocast_dtype, cache_enabled=False):
-                loss, logits = self.model.forward_loss(feature, mask, labels, **kw)
-        else:
+        with _autocast(self.autocast_dtype, cache_enabled=False):
             loss, logits = self.model.forward_loss(feature, mask, labels, **kw)
         self.logits = logits.detach()
         loss = loss / self.args.trg_accumulation_steps

@@ -83,7 +83,7 @@ def _worker(rank, port, out_dir):
             avg = GradientAverager([p for p in mm.parameters() if p.requires_grad], hooks=False, bucket_mb=1, always=True) if exchange else None
             step = GraphedTargetStep(swin, mm, opt, None, cfg, batches[0], autocast_dtype=None, frame_capacity=BUCKETS, averager=avg)
             assert step.split == exchange and step.capacities == BUCKETS and step.replays == {8: 0, 12: 0}
-            assert (set(step._graphs_a2) == set(BUCKETS)) == exchange and len(step._graphs) == 2
+            assert sorted(step._captures) == [(c, True) for c in BUCKETS] and all((r.a2 is not None) == exchange for r in step._captures.values())
             losses, kept, counts, caps = [], [], [], []
             for i in range(6):
                 loss, k = step(batches[i % len(batches)])

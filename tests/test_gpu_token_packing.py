@@ -263,9 +263,10 @@ def _small_roberta(p=0.0):
     return RobertaModel(cfg, add_pooling_layer=False)
 
 
-def _step(dev, token_capacity, frame_capacity=CAP, adamw=False):
+def _step(dev, token_capacity, frame_capacity=CAP, adamw=False, exchange=False):
     """the models and batch of tests/test_gpu_ragged_step.py (fp32 fusion stack and Swin, tau = 1e5, dropout and DropPath off, SGD, frame capacity 12)
-    with a two-layer bf16 RoBERTa (2 heads x 64) under MasterWeights as the text encoder, so that the fused encoder -- the thing that packs -- runs"""
+    with a two-layer bf16 RoBERTa (2 heads x 64) under MasterWeights as the text encoder, so that the fused encoder -- the thing that packs -- runs.
+    `exchange` (needs an initialised process group): under GradientAverager(always=True, hooks=False, bucket_mb=1), the two-piece mode"""
     import bench
     from facialmmt_amd import models, synth
     from facialmmt_amd.config import default_args
@@ -300,8 +301,12 @@ def _step(dev, token_capacity, frame_capacity=CAP, adamw=False):
         opt = HFAdamW(step_parameters(mm, masters), lr=torch.tensor(1e-5, device=dev), weight_decay=0.01)
     else:
         opt = torch.optim.SGD(step_parameters(mm, masters), lr=0.05)
+    avg = None
+    if exchange:
+        from facialmmt_amd.parallel import GradientAverager
+        avg = GradientAverager(step_parameters(mm, masters), hooks=False, bucket_mb=1, always=True)
     step = GraphedTargetStep(swin, mm, opt, None, cfg, tuple(batch), autocast_dtype=None, masters=masters, frame_capacity=frame_capacity,
-                             token_capacity=token_capacity)
+                             token_capacity=token_capacity, averager=avg)
     return step, mm, masters, tuple(batch)
 
 
@@ -326,10 +331,10 @@ def test_graphed_step_on_packed_tokens_matches_the_padded_step():
         total, prefix = ts.count_tokens(batch[1])
         assert prefix and 0 < total < batch[1].numel()
         if side == "packed":
-            assert step.token_capacity == (total + ts.TOKEN_GRANULE - 1) // ts.TOKEN_GRANULE * ts.TOKEN_GRANULE and None in step._padded_graphs
+            assert step.token_capacity == (total + ts.TOKEN_GRANULE - 1) // ts.TOKEN_GRANULE * ts.TOKEN_GRANULE and (CAP, False) in step._captures
             assert getattr(mm, "text_token_capacity", 0) == 0       # nobody else who calls the model runs packed
         else:
-            assert step.token_capacity == 0 and not step._padded_graphs
+            assert step.token_capacity == 0 and not [k for k in step._captures if not k[1]]
         before = _sample(mm, masters)
         loss, kept = step(batch)
         torch.cuda.synchronize()
@@ -390,7 +395,7 @@ def test_graphed_step_with_three_frame_capacities_packs_and_keeps_a_twin_per_cap
         step, mm, masters, batch = _step(dev, tc, frame_capacity=caps, adamw=True)
         assert step.fused is not None and step.handover is not None
         if side == "packed":
-            assert step.token_capacity > 0 and sorted(step._padded_graphs) == list(caps)
+            assert step.token_capacity > 0 and sorted(c for c, packed in step._captures if not packed) == list(caps)
             assert sorted(step.twin_capture_bytes) == sorted(step.twin_capture_reserved_bytes) == list(caps) == sorted(step.capture_bytes)
         holed = batch[1].clone()
         holed[0, 3] = 0
