@@ -141,13 +141,14 @@ __global__ __launch_bounds__(256) void wattn_fwd_kernel(WaArgs p) {
                 tmax = fmaxf(tmax, v);
             }
             const float mnew = fmaxf(mx, tmax);
-            const float alpha = __expf(mx - mnew);
+            const float mref = mnew == -INFINITY ? 0.f : mnew;      // a tile of -inf logits (mask): as in mha_fwd_kernel
+            const float alpha = __expf(mx - mref);
             l *= alpha;
 #pragma unroll
             for (int d = 0; d < HD; ++d) o[d] *= alpha;
 #pragma unroll
             for (int jj = 0; jj < WS; ++jj) {
-                const float e = __expf(s[jj] - mnew);
+                const float e = __expf(s[jj] - mref);
                 l += e;
                 lds_axpy32(o, e, &Vs[wave][(j0 + jj) * KP]);
             }
@@ -443,13 +444,14 @@ __global__ __launch_bounds__(64) void mha_fwd_kernel(MhaArgs p) {
                 tmax = fmaxf(tmax, s[jj]);
             }
             const float mnew = fmaxf(m, tmax);
-            const float alpha = __expf(m - mnew);          // m = -inf on the first tile -> 0
+            const float mref = mnew == -INFINITY ? 0.f : mnew;      // every key so far at -inf (key_bias): exp(-inf - 0) = 0, where -inf - -inf would be NaN
+            const float alpha = __expf(m - mref);          // m = -inf on the first tile -> 0
             l *= alpha;
 #pragma unroll
             for (int d = 0; d < D; ++d) o[d] *= alpha;
 #pragma unroll
             for (int jj = 0; jj < 8; ++jj) {
-                const float e = __expf(s[jj] - mnew);       // -inf -> 0
+                const float e = __expf(s[jj] - mref);       // -inf -> 0
                 l += e;
                 const float ks = keep_scale(p, bh, i, j0 + js + jj);
                 laxpy<D>(o, e * ks, Vs + (js + jj) * P);

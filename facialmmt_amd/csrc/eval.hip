@@ -64,12 +64,14 @@ __global__ __launch_bounds__(EH_THREADS) void emotion_head_kernel(int N, int K, 
         const bool live = c < NL;
         float s = -INFINITY;
         if (live) {
-            s = b2[c];
+            s = 0.f;                                        // the bias is added to the finished sum: 64 roundings at a +-1e4 bias's magnitude would cost 1e-3 of a probability
             const float* wc = w2 + c * EH_HID;
             for (int j = 0; j < EH_HID; ++j) {
-                const float h = fmaxf(hpart[0][r][j] + hpart[1][r][j] + b1[j], 0.f);
+                const float pre = hpart[0][r][j] + hpart[1][r][j] + b1[j];
+                const float h = pre < 0.f ? 0.f : pre;               // torch.relu: a NaN feature stays NaN (fmaxf would return the 0)
                 s = fmaf(h, wc[j], s);
             }
+            s += b2[c];
             if (gumbel != nullptr && grow < N) s += gumbel[(size_t)grow * NL + c];
             s = s / tau;
         }

@@ -69,6 +69,14 @@ int fmmt_version(void);
  *   - FMMT_EPI_GELU: if y_pre != NULL the pre-activation (acc + bias) is stored there as well;
  *   - FMMT_EPI_GELU_BWD: aux[M,N] (dtype) holds the saved pre-activation;
  *   - FMMT_EPI_GELU_DG: y_pre (may be NULL) receives gelu'(acc + bias); FMMT_EPI_MUL_AUX: aux[M,N] (dtype) holds that derivative.
+ * Non-finite values: a NaN or infinity in x, w, bias, res or a MUL_AUX aux comes out non-finite in every output element that depends on it and
+ * nowhere else, with ONE documented exception: the bf16 GELU forms (FMMT_EPI_GELU, _GELU_DG, _GELU_BWD here, and the hidden layer of fmmt_mlp_fwd /
+ * fmmt_mlp_ln_fwd / fmmt_mlp_bwd_input) clamp their argument with a maximum, which returns its finite operand: a NaN pre-activation gives
+ * gelu ~ -1e-18 and gelu' = 1, and gelu'(+inf) = 1.  What a caller can rely on instead: the stored pre-activation (FMMT_EPI_GELU's y_pre,
+ * fmmt_mlp_fwd's h_pre) is NaN, and a residual operand carries the poisoned element itself through -- y = x + Mlp(x) and y = x + Mlp(LayerNorm(x))
+ * are NaN at that element, and the next LayerNorm makes its whole row NaN; the attention half of a Swin block (fmmt_window_block_fwd) makes every
+ * row of the poisoned token's window NaN.  fp32 propagates everywhere, the Mlp's whole row included.
+ * tests/test_gpu_value_edges.py holds all of this, the exception included.
  * The same entry point computes input gradients: dx[M,K] = dy[M,N] . (w^T)[K,N]^T with a transposed
  * copy of the weight.
  * Leading dimensions: every operand and output may be a view with a row pitch larger than its width (a slice of a packed buffer, a padded
@@ -305,6 +313,10 @@ int fmmt_window_block_attn_bwd_ref(int dtype, int n_img, int H, int W, int C, in
  * cross-modal encoder passes NULL (it has no key-padding mask at all); the per-modality self-attention encoders
  * (modules/Transformer.py:93-95 `attention_scores + attention_mask`, mask built at src/models.py:157,164 as
  * (1 - m) * -10000) pass their extended attention mask squeezed to [B, Lk].  No gradient is produced for it.
+ * Values: any finite number, and -inf (or a finite value the fp32 logit cannot absorb, such as -FLT_MAX) on SOME keys of a batch element, in any
+ * position -- leading, whole key tiles, scattered, all but one: such a key gets probability exactly 0 and no gradient, as in torch.softmax; both
+ * kernel families agree (tests/test_gpu_value_edges.py).  A batch element whose keys are ALL at -inf is outside the contract (its softmax is 0 / 0).
+ * Non-finite operands: a NaN in q, k or v comes out as NaN in every output element that depends on it and nowhere else.
  * Leading dimensions (the rules of fmmt_mha_fwd_ragged / _bwd_ragged, fmmt_tokens.h): ldq (q), ldkv (k, v), ldo (out AND dout), lddq (dq), lddkv (dk, dv)
  * are independent row pitches in elements; each is >= E, else FMMT_EINVAL, and a multiple of 16 bytes (bf16: 8 elements, f32: 4), else FMMT_EALIGN --
  * every kernel, VALU and matrix-core, moves 16-byte vectors at row * ld + head * head_dim, so no kernel serves another pitch (until the kernel-bounds
