@@ -162,7 +162,7 @@ __global__ __launch_bounds__(512) void linear_nt_ph3_kernel(LinArgs p) {
 
     // ---- drip epilogue ----
     bf16x8 rb[4];
-    bf16x8 rg[4];                                              // EPI 3: the GELU rows beside the pre-activation rows in rb; EPI 6: the rounding residuals of rb
+    bf16x8 rg[4];                                              // EPI 3: the GELU rows beside the pre-activation rows in rb; EPI 5 / 6: the lower halves of the fp32 words whose upper halves are in rb
     float rsv[4];                                              // EPI 5 / 6: DropPath scale of the four 8-row blocks' rows
     float* const rslab = reinterpret_cast<float*>(smem + 2 * BUF + 8 * (16 * 144) + 8 * 512) + wave * 256;   // two 128-float slots by tile parity: rowscale of this wave's 96 rows
     int em0 = 0, en0 = 0;
@@ -195,21 +195,29 @@ __global__ __launch_bounds__(512) void linear_nt_ph3_kernel(LinArgs p) {
                     tv[c][e] = acc[a0 + t][2 * c + (e >> 2)][e & 3] + bb[2 * c + (e >> 2)][e & 3];
                     v[e] = (bf16)tv[c][e];
                 }
+                if constexpr (EPI == 5 || EPI == 6) {          // the fp32 words' upper halves, NOT a rounding (whole 32-bit words: element e in the low or high half of word e / 2)
+                    u32x4 hw;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) hw[j] = (__builtin_bit_cast(unsigned, tv[c][2 * j]) >> 16) | (__builtin_bit_cast(unsigned, tv[c][2 * j + 1]) & 0xFFFF0000u);
+                    v = __builtin_bit_cast(bf16x8, hw);
+                }
                 *reinterpret_cast<bf16x8*>(wslab + li * 144 + (c * 32 + lg * 8) * 2) = v;
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h) rb[2 * t + h] = *reinterpret_cast<const bf16x8*>(wslab + (h * 8 + rr) * 144 + rc * 16);
-            if constexpr (EPI == 6) {
-                // the product with the stored derivative is formed on the read-back side, where the value has been rounded to bf16 once already: a second pass
-                // carries the rounding residual (value - bf16(value), itself to bf16: 2^-17 relative together), so that y = (hi + lo) * aux * scale rounds ONCE.
-                // (Without it the whole-Swin bf16 gradient statistics went from 0.089 to 0.10-0.12 relative L2 against the fp32 oracle: every Mlp backward of
-                // stages 1-3 rounded d(hidden) twice.)
+            if constexpr (EPI == 5 || EPI == 6) {
+                // the residual add / the product with the stored derivative is formed on the read-back side, in fp32 on the fp32 value: the slab carries the
+                // accumulator's 32-bit word in two passes (upper half above, lower half here), so that y = res + scale * value and y = value * aux * scale
+                // round ONCE, as nt_epilogue does.  (EPI 5 used to send bf16(value) alone: every proj / fc2 forward of stages 1-3 rounded the branch before the
+                // residual add -- tests/test_gpu_gemm_exact.py: 18-25 % of the elements off the single rounding; EPI 6 sent bf16(value) + bf16(value -
+                // bf16(value)), 2^-17 relative, after the whole-Swin bf16 gradient statistics had gone from 0.089 to 0.10-0.12 relative L2 against the fp32
+                // oracle with one pass.)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    bf16x8 v;
+                    u32x4 lw;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (bf16)(tv[c][e] - (float)(bf16)tv[c][e]);
-                    *reinterpret_cast<bf16x8*>(wslab + li * 144 + (c * 32 + lg * 8) * 2) = v;
+                    for (int j = 0; j < 4; ++j) lw[j] = (__builtin_bit_cast(unsigned, tv[c][2 * j]) & 0xFFFFu) | (__builtin_bit_cast(unsigned, tv[c][2 * j + 1]) << 16);
+                    *reinterpret_cast<u32x4*>(wslab + li * 144 + (c * 32 + lg * 8) * 2) = lw;
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) rg[2 * t + h] = *reinterpret_cast<const bf16x8*>(wslab + (h * 8 + rr) * 144 + rc * 16);
@@ -277,13 +285,19 @@ __global__ __launch_bounds__(512) void linear_nt_ph3_kernel(LinArgs p) {
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {               // four elements at a time, one row block after the other: the polynomial's temporaries are what spills
                     float v[4], a[4];
+                    const u32x4 hw = __builtin_bit_cast(u32x4, rb[i]), lw = __builtin_bit_cast(u32x4, rg[i]);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] = (float)rb[i][4 * hf + e]; a[e] = (float)o[4 * hf + e]; }
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (EPI == 4) v[e] = (float)rb[i][4 * hf + e];
+                        else if (e & 1) v[e] = __builtin_bit_cast(float, (hw[2 * hf + (e >> 1)] & 0xFFFF0000u) | (lw[2 * hf + (e >> 1)] >> 16));      // the fp32 value itself
+                        else v[e] = __builtin_bit_cast(float, (hw[2 * hf + (e >> 1)] << 16) | (lw[2 * hf + (e >> 1)] & 0xFFFFu));
+                        a[e] = (float)o[4 * hf + e];
+                    }
                     if constexpr (EPI == 4) {
                         q3_gelu_grad_mul<4>(v, a);
                     } else if constexpr (EPI == 6) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = a[e] * (rsv[i] * (v[e] + (float)rg[i][4 * hf + e]));
+                        for (int e = 0; e < 4; ++e) v[e] = a[e] * (rsv[i] * v[e]);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = a[e] + rsv[i] * v[e];

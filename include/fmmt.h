@@ -87,6 +87,20 @@ int fmmt_version(void);
  * Anything else returns FMMT_EINVAL before any launch (bf16 with N or an ld congruent to 4 mod 8 was accepted until the strided GEMM tests:
  * no kernel handles it with naturally aligned accesses; DESIGN.md "Leading dimensions of the GEMMs").  fmmt_linear_fwd_seg3 holds
  * ldy, and fmmt_linear_fwd_splitk N and ldy, to the same rule.
+ * Rounding (every route of enum fmmt_route, fmmt_linear_fwd_seg3 / _splitk / _wgrad included; tests/test_gpu_gemm_exact.py holds it bit for bit):
+ *   - products of the operands are exact and are accumulated in fp32, in an order that depends on the route (tile, K split, pipeline depth);
+ *   - bias, activation, aux product, row scale and residual are applied in fp32, in this order: v = acc + bias; y_pre = v (FMMT_EPI_GELU);
+ *     v = epi(v); v = v * rowscale; v = v + res;
+ *   - every stored element (y, y_pre) is ONE round-to-nearest-even of that fp32 value to the element type; nothing is rounded in between;
+ *   - split-K and weight-gradient partials are fp32 and are summed in fp32; dw and db are fp32 and are not rounded at all.
+ * So for operands whose products and partial sums are integers below 2^24 every output is the exact result rounded once, whatever the route.
+ * Exceptions, by route (each a rounding BELOW fp32 in front of the contraction; none behind it):
+ *   - fmmt_linear_wgrad with a rowscale on the register-staged kernels (FMMT_ROUTE_TN_REG32, _TN_REG32_FEW, _TN_REG64): s_m * dy is rounded to the
+ *     element type before the MFMA, and db sums the rounded values.  The DMA-staged kernels (_TN_DMA_*_SCALED) apply a two-valued scale vector
+ *     (0 and one other value per token range: what DropPath hands over) to the fp32 accumulators, exactly; any other vector is rounded the same way.
+ *   - x_epi = FMMT_EPI_GELU: gelu(x) is rounded to the element type before the MFMA.
+ * The GELU forms themselves (FMMT_EPI_GELU's y, _GELU_DG, _GELU_BWD) are polynomial / table evaluations in fp32 with one rounding at the store;
+ * their accuracy is held by tests/test_gpu_value_edges.py, not bit for bit.
  */
 int fmmt_linear_fwd(int dtype, int M, int N, int K,
                     const void* x, int ldx, const void* w, int ldw, const float* bias,
