@@ -6,9 +6,11 @@
 // Both keep the *weight* on the MFMA "A" side and the *activation* on the "B" side, so the
 // accumulator fragment of a lane is a run of consecutive output channels of ONE token: the
 // epilogue (bias, GELU, residual, DropPath scale) works on contiguous vectors and stores rows.
+// Which kernel a call takes -- dispatch_nt, p256_plan, ph_plan, splitk_plan, tn_plan, tn_plan_dma, tn_few_ok, launch_tn_plan -- lives in gemm_plan.h.
 #include "gemm_common.h"
 #include "gemm_ph.h"
 #include "gemm_ph3.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -998,272 +1000,57 @@ __global__ __launch_bounds__(512) void linear_nt_p256_kernel(LinArgs p) {
     }
 }
 
+// Launchers: one per kernel family, one entry of LAUNCH (end of this file) per instantiation.  A launcher raises its kernel's dynamic-LDS
+// limit once per device, fills the tile fields from the plan and launches; which of them a call takes is gemm_plan.h's decision alone.
+template <typename Args>
+int launch_once(void (*kernel)(Args), FmmtLdsOnce& lds_once, size_t lds, dim3 grid, int threads, hipStream_t st, const Args& p) {
+    if (int rc_ = lds > 65536 ? lds_once.set(reinterpret_cast<const void*>(kernel), (int)lds) : 0) return rc_;
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, p);
+    FMMT_CHECK_LAUNCH();
+    return 0;
+}
+LinArgs with_tiles(const LinArgs& a, const GemmPlan& pl) {
+    LinArgs p = a;
+    p.tiles_m = pl.tiles_m, p.tiles_n = pl.tiles_n;
+    return p;
+}
+
 template <int BN, int BK, int NBUF, bool BATCH, bool HASOP, bool PIPE = false>
-int launch_p256_b(const LinArgs& a, hipStream_t st, int* route) {
+int launch_p256_b(const LinArgs& a, const GemmPlan& pl, hipStream_t st) {
     constexpr size_t lds = (size_t)NBUF * (BN + 256) * BK * 2 + 2 * 256 * sizeof(float) + (BN == 256 ? 8 * 16 * 144 : 2 * (BN == 192 ? 32 : 16) * (BN * 2 + 16));   // ring, bias slabs, epilogue scratch (BN = 256: wave-private slabs)
     static_assert(lds <= 160 * 1024, "LDS");
     static FmmtLdsOnce lds_once;
-    if (route) { *route = (BN == 256 ? FMMT_ROUTE_P256_256 : BN == 192 ? FMMT_ROUTE_P256_192 : FMMT_ROUTE_P256_128) + (HASOP ? 2 : PIPE ? 1 : 0); return 0; }
-    if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_nt_p256_kernel<BN, BK, NBUF, BATCH, HASOP, PIPE>), (int)lds)) return rc_;
-    LinArgs p = a;
-    p.tiles_m = (a.M + 255) / 256;
-    p.tiles_n = a.N / BN;
-    hipLaunchKernelGGL((linear_nt_p256_kernel<BN, BK, NBUF, BATCH, HASOP, PIPE>), dim3(256), dim3(512), lds, st, p);
-    FMMT_CHECK_LAUNCH();
-    return 0;
-}
-template <int BN, int BK, int NBUF>
-int launch_p256(const LinArgs& a, hipStream_t st, int* route) {
-    if constexpr (BN != 256) {
-        // launches with an M x N epilogue operand or a DropPath scale: operand prefetched into registers (48 / 32 of them:
-        // no room beside the 128 accumulators of the 256-wide tile).  (Operand-free launches that store directly, K > 1536, were tried
-        // on this instantiation as well: against the pipelined loop below it loses, 135 -> 127 us, same call.)
-        if (a.res || a.aux || a.rowscale) return launch_p256_b<BN, BK, NBUF, true, true>(a, st, route);
-    }
-    // Pipelined fragment reads + DMA pieces in groups (PIPE), for K >= 384.  Same-call A/B against the plain loop, us per
-    // launch: 31360 x 2304 x 768 124 -> 115, 31360 x 3072 x 768 150 -> 141, 31360 x 768 x 768 44.4 -> 41.2, 125440 x 1536 x 384
-    // (256-wide tile, one group) 190 -> 178, 125440 x 384 x 384 52.7 -> 50.2, 125440 x 1152 x 384 / 384 x 1536 / 384 x 1152 +-1 %;
-    // K = 192 (three K steps per tile: the late pieces are waited for) 210 -> 220, stays on the plain loop.
-    if (a.K >= 384) return launch_p256_b<BN, BK, NBUF, true, false, true>(a, st, route);
-    return launch_p256_b<BN, BK, NBUF, true, false>(a, st, route);
+    return launch_once(&linear_nt_p256_kernel<BN, BK, NBUF, BATCH, HASOP, PIPE>, lds_once, lds, dim3(pl.grid), 512, st, with_tiles(a, pl));
 }
 
-// Tile choice for the persistent kernel: the widest channel tile that divides N, unless a narrower one fills the last
-// round of 256 workgroups better (31360 tokens x 768 channels: 369 tiles of 256 x 256 = 2 rounds at 72 %, 492 tiles of
-// 256 x 192 = 2 rounds at 96 %).  Returns 0 if the shape is not for this kernel.
-int p256_plan(const LinArgs& a) {
-    constexpr int P256_MINM = 16384;                       // fewest tokens for this kernel
-    // (K % 64 != 0 -- Swin stage 0: K = 96 -- stays on the deep / single-step kernels)
-    if (a.ksplit || a.M < P256_MINM || a.M % 16 || a.K % 64 || a.K < 96 || a.ldx % 8 || a.ldw % 8) return 0;
-    if ((unsigned long long)a.M * a.ldx >= (1ull << 31) || (unsigned long long)a.N * a.ldw >= (1ull << 31)) return 0;   // 32-bit byte offsets of the DMA pieces
-    // One workgroup per CU has nothing to hide an epilogue's own M x N loads behind (residual, GELU' operand, DropPath
-    // scale: the in-order vmcnt also makes them wait for the DMA stages in flight).  Measured on MI355X
-    // (profiles/r02_gemm_shapes.txt): plain / bias / GELU + pre-activation launches gain 5-50 % over the two-workgroup
-    // 256 x 128 kernels (125440 x 1536 x 384 GELU: 0.439 -> 0.295 ms).
-    // Launches with a residual and / or DropPath scale come here too, on the 192- / 128-wide tiles, with the operand prefetched
-    // into registers one K step before the epilogue (HASOP): measured, same call, 321 -> 262 us (501760 x 192 x 768), 210 -> 201
-    // (125440 x 384 x 1536).  GELU' launches (an aux operand) do not: 338 -> 391 / 530 -> 614 us -- that epilogue is ~11 k VALU
-    // cycles per wave tile against 4.6 k MFMA cycles of a K = 384 tile, and one workgroup per CU has no second workgroup whose K
-    // loop could run under it.
-    // (round 4: re-measured with gelu' from an LDS table in this kernel's unused epilogue scratch instead of the polynomial: 125440 x 1536 x 384
-    //  328 -> 364 us, 501760 x 768 x 192 522 -> 561, 31360 x 3072 x 768 267 -> 253 -- still a loss where it matters.
-    //  And once more with the polynomial GELU' that replaced the tables: 314 -> 340, 491 -> 529, 258 -> 241 us.)
-    const bool has_op = a.res || a.aux || a.rowscale;
-    if (has_op && (a.aux || a.ldres % 8 || a.ldaux % 8)) return 0;
-    const int tm = (a.M + 255) / 256;
-    int best = 0;
-    double best_cost = 0;
-    const int cand[3] = {256, 192, 128};
-    const double pen[3] = {1.0, 1.04, 1.10};
-    for (int i = 0; i < 3; ++i) {
-        const int bn = cand[i];
-        if (a.N % bn) continue;
-        if (has_op && bn == 256) continue;
-        const int tiles = tm * (a.N / bn);
-        if (tiles < 256) continue;
-        const double cost = (double)((tiles + 255) / 256) * bn * pen[i];
-        if (!best || cost < best_cost) {
-            best = bn;
-            best_cost = cost;
-        }
-    }
-    return best;
-}
-
-// the FMMT_ROUTE_* value of a linear_nt_kernel instantiation (BN = 96 / 128 share one)
-template <typename T, int BM, int BK, int NBUF, bool GLDS, bool SEG>
-constexpr int nt_route() {
-    if (sizeof(T) == 4) return BM == 64 ? FMMT_ROUTE_NT64_F32 : FMMT_ROUTE_NT128_F32;
-    if (BM == 32) return (SEG ? FMMT_ROUTE_NT_SEG3 : FMMT_ROUTE_NT_QUARTER) + (NBUF == 4 ? 1 : 0);
-    if (BM == 64) return NBUF == 1 ? (BK == 96 ? FMMT_ROUTE_NT64_K96 : FMMT_ROUTE_NT64_K64) : GLDS ? (NBUF == 4 ? FMMT_ROUTE_NT64_DMA_R4 : FMMT_ROUTE_NT64_DMA)
-                                   : BK == 64 ? FMMT_ROUTE_NT64_BK64 : FMMT_ROUTE_NT64_BK32;
-    return NBUF == 1 ? (BK == 96 ? FMMT_ROUTE_NT128_K96 : FMMT_ROUTE_NT128_K64) : GLDS ? FMMT_ROUTE_NT128_DMA : BK == 64 ? FMMT_ROUTE_NT128_BK64 : FMMT_ROUTE_NT128_BK32;
-}
 template <typename T, int BM, int BN, int BK, int NBUF, bool GLDS = false, bool SEG = false>
-int launch_nt(const LinArgs& a, hipStream_t st, int* route) {
+int launch_nt(const LinArgs& a, const GemmPlan& pl, hipStream_t st) {
     constexpr int VEC = Vec<T>::N;
     constexpr size_t lds = (size_t)NBUF * (BM + BN) * (GLDS ? BK : BK + VEC) * sizeof(T);
     static FmmtLdsOnce lds_once;
-    if (route) { *route = nt_route<T, BM, BK, NBUF, GLDS, SEG>(); return 0; }
-    if (lds > 65536) {
-        if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_nt_kernel<T, BM, BN, BK, NBUF, GLDS, SEG>), (int)lds)) return rc_;
-    }
-    LinArgs p = a;
-    p.tiles_n = (a.N + BN - 1) / BN;
-    p.tiles_m = (a.M + BM - 1) / BM;
-    const int grid = p.tiles_m * p.tiles_n;
-    const int splits = a.ksplit ? (a.K + a.ksplit - 1) / a.ksplit : 1;
-    hipLaunchKernelGGL((linear_nt_kernel<T, BM, BN, BK, NBUF, GLDS, SEG>), dim3(grid, splits), dim3(256), lds, st, p);
-    FMMT_CHECK_LAUNCH();
-    return 0;
+    return launch_once(&linear_nt_kernel<T, BM, BN, BK, NBUF, GLDS, SEG>, lds_once, lds, dim3(pl.grid, pl.splits), 256, st, with_tiles(a, pl));
+}
+// the 64- / 128-row kernels: 96- and 128-channel tiles share a route
+template <typename T, int BM, int BK, int NBUF, bool GLDS = false>
+int launch_nt_bn(const LinArgs& a, const GemmPlan& pl, hipStream_t st) {
+    return pl.bn == 96 ? launch_nt<T, BM, 96, BK, NBUF, GLDS>(a, pl, st) : launch_nt<T, BM, 128, BK, NBUF, GLDS>(a, pl, st);
 }
 
-template <typename T, int BM, int BN>
-int dispatch_nt_bk(const LinArgs& a, hipStream_t st, int* route) {
-    if constexpr (sizeof(T) == 2) {
-        // Swin stage 0: one K step.  (64- and 256-row tiles measured: no gain / -35 %.)  These launches are HBM streams
-        // (40-70 FLOP/B); epilogue-shaped stores alone reach 5.5 TB/s on this part (profiles/r01_hbm_calibration.txt), what
-        // holds a single-step workgroup at ~3 TB/s is its load -> LDS -> MFMA -> store chain with nothing to overlap, so
-        // occupancy is what counts (NtWaves above); the fc1 + GELU + pre-activation launch is the only one still on it.
-        if (!a.ksplit && a.K == 96) return launch_nt<T, BM, BN, 96, 1>(a, st, route);
-        if (!a.ksplit && a.K <= 64) return launch_nt<T, BM, BN, 64, 1>(a, st, route);     // PatchEmbed (K = 48)
-        // measured on MI355X (tools/probes/gemm_bench.py, sum over the bench shapes): BK=64 5.33 ms vs BK=32 5.88 ms
-        // direct global->LDS DMA staging: measured +7 % over register staging summed over the bench shapes, up to
-        // +25 % on the K >= 768 ones (971 TF/s on 31360x768x3072)
-        if (a.K % 64 == 0 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
-            // four-buffer ring for few-token problems with a long K loop and at most one workgroup per CU (fc2 of the
-            // encoder FFNs, 512-1328 tokens x 768 x 3072: 32 -> 25 us); with more tiles than CUs the 96 KB ring costs
-            // co-residency (1328 x 3072 x 768: 15 -> 21 us), and at K = 768 it is a wash.
-            if constexpr (BM == 64) {
-                const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-                if (a.K >= 2048 && tiles <= 256) return launch_nt<T, BM, BN, 64, 4, true>(a, st, route);
-            }
-            return launch_nt<T, BM, BN, 64, 2, true>(a, st, route);
-        }
-        if (a.K % 64 == 0 && (!a.ksplit || a.ksplit % 64 == 0)) return launch_nt<T, BM, BN, 64, 2>(a, st, route);
-        return launch_nt<T, BM, BN, 32, 2>(a, st, route);
-    } else {
-        return launch_nt<T, BM, BN, 16, 2>(a, st, route);                                 // fp32 parity path
-    }
+int launch_deep(const LinArgs& a, const GemmPlan& pl, hipStream_t st) {
+    static FmmtLdsOnce lds_once;
+    return launch_once(&linear_nt_deep_kernel, lds_once, (size_t)3 * (256 + 128) * 64 * 2, dim3(pl.grid), 512, st, with_tiles(a, pl));
+}
+template <int NK, int BN>
+int launch_deep32(const LinArgs& a, const GemmPlan& pl, hipStream_t st) {
+    static FmmtLdsOnce lds_once;
+    return launch_once(&linear_nt_deep32_kernel<NK, BN>, lds_once, (size_t)3 * (256 + BN) * 32 * 2, dim3(pl.grid), 512, st, with_tiles(a, pl));
 }
 
-// The phase-structured kernels (gemm_ph.h: 256 x 256 tiles, four phases; gemm_ph3.h: 192 x 256 tiles, three phases, all epilogues but GELU').
-// Returns 0 (none), 1 (gemm_ph.h, plain / bias), 3 (gemm_ph3.h, 192 x 256 tiles) or 4 (gemm_ph3.h, 384 x 128 tiles); *epi3 = gemm_ph3.h's EPI template value:
-// 2 plain / bias, 3 GELU + pre-activation, 5 residual / row scale, 6 product with the stored GELU derivative (+ row scale).
-// Measured against the kernels below and each other (tools/probes/nt_ph_probe.hip, same call, us per launch, production -> ph / ph3):
-//   plain / bias     31360 x 768 x 3072 136 -> 139 / 110 (369 tiles of 256 x 256 = 1.44 rounds of 256 workgroups, 492 of 192 x 256 = 1.92), x 768 x 768 42 -> 44 / 35,
-//                    x 2304 x 768 113 -> 101 / 100, x 3072 x 768 143 -> 129 / 132, 125440 x 1536 x 384 190 -> 154 / 167, 7840 x 1536 x 6144 168 -> 134 / 106,
-//                    7840 x 6144 x 1536 186 -> 116 / 123, 7840 x 1536 x 1536 38.5 (128-row kernels) -> 38 / 31: the tile whose rounds waste less wins;
-//   res + row scale  31360 x 768 x 3072 156 -> 117, x 768 x 768 56 -> 42, x 3072 x 768 235 -> 161, 125440 x 1536 x 384 318 -> 242, 7840 x 1536 x 6144 169 -> 110 (ph3 only);
-//   GELU + pre       wins from K = 1536 (7840 x 6144 x 1536 211 -> 184, 31360 x 768 x 3072 159 -> 141), loses below (31360 x 3072 x 768 195 -> 254: the polynomial runs
-//                    behind the MFMAs of a phase, on the workgroup's critical path, and a short K loop has few phases to amortise it);
-//   GELU'            loses everywhere (262 -> 828): stays on the persistent kernel.
-int ph_plan(const LinArgs& a, int* epi3) {
-    const bool mul_aux = a.epi == FMMT_EPI_MUL_AUX && a.aux && !a.res && !a.y_pre && !a.bias;
-    if (a.ksplit || a.part || (a.aux && !mul_aux)) return 0;
-    const bool gelu_pre = a.epi == FMMT_EPI_GELU && a.y_pre, has_op = a.res || a.rowscale;
-    if (!gelu_pre && !mul_aux && (a.epi != 0 || a.y_pre)) return 0;
-    if (gelu_pre && (has_op || a.K < 1536)) return 0;
-    if (mul_aux && (a.ldaux % 8 || (unsigned long long)a.M * a.ldaux >= (1ull << 31))) return 0;
-    if (a.M < 4096 || a.M % 8 || a.N % 128 || a.K % 64 || a.K < 192 || a.ldx % 8 || a.ldw % 8 || a.ldy % 8) return 0;
-    if (a.res && a.ldres % 8) return 0;
-    if (a.rowscale && a.rows_per_scale <= 0) return 0;
-    if ((unsigned long long)a.M * a.ldx >= (1ull << 31) || (unsigned long long)a.N * a.ldw >= (1ull << 31) || (unsigned long long)a.M * a.ldy >= (1ull << 31) ||
-        (a.res && (unsigned long long)a.M * a.ldres >= (1ull << 31)))
-        return 0;
-    if (a.N % 256) {
-        // channel counts that are multiples of 128 only (Swin stage 2: 384, 1152): gemm_ph3.h's 384-token x 128-channel layout (returns 4).  Measured at 125440 tokens
-        // (production -> ph3): x 1152 x 384 134 -> 129, x 384 x 384 45.5 -> 43.6, with residual + row scale 240 -> 204 / 79 -> 58, row scale alone 59 -> 54.5;
-        // at K = 1152 / 1536 it loses (164 -> 166, with residual 181 -> 196: three channel tiles per token panel, 96 FLOP per staged byte): K <= 512 only.
-        if (gelu_pre || a.K > 512) return 0;
-        const long long t384 = (long long)((a.M + 383) / 384) * (a.N / 128), r384 = (t384 + 255) / 256;
-        if (t384 < 256 || t384 * 100 < r384 * 256 * 85) return 0;
-        *epi3 = mul_aux ? 6 : has_op ? 5 : 2;
-        return 4;
-    }
-    const long long t256 = (long long)((a.M + 255) / 256) * (a.N / 256), t192 = (long long)((a.M + 191) / 192) * (a.N / 256);
-    const long long r256 = (t256 + 255) / 256, r192 = (t192 + 255) / 256;
-    const long long min_tiles = a.M < 16384 ? 150 : 256;        // 16384+ tokens: the persistent 256-row kernel's ground, taken only with (nearly) full rounds
-    const bool ok256 = t256 >= min_tiles && (a.M < 16384 || t256 * 100 >= r256 * 256 * 85);
-    const bool ok192 = t192 >= min_tiles && (a.M < 16384 || t192 * 100 >= r192 * 256 * 85);
-    *epi3 = gelu_pre ? 3 : mul_aux ? 6 : has_op ? 5 : 2;
-    if (gelu_pre || has_op || mul_aux) return ok192 ? 3 : 0;
-    // plain / bias: rows of MFMA work per workgroup over the launch; the 192-row tile is charged 3 % (shorter phases per byte staged)
-    const long long c256 = r256 * 256 * 100, c192 = r192 * 192 * 103;
-    if (ok192 && (!ok256 || c192 < c256)) return 3;
-    return ok256 ? 1 : 0;
-}
-
-template <typename T>
-int dispatch_nt(const LinArgs& a, hipStream_t st, int* route) {
-    // BN = 96 when it tiles N exactly and 128 would not (C = 96, 288, 192, 576 ...)
-    const bool n96 = (a.N % 96 == 0) && (a.N % 128 != 0);
-    // few-token problems (cross-modal encoder: 152..1280 rows; embedding head: 640 rows) use 64-row tiles so
-    // that twice as many workgroups share the work; the multi-million-token Swin GEMMs use 128-row tiles
-    // (few rows but tens of thousands of output channels -- the input gradient of the 37632 -> 512 embedding head: there are
-    //  workgroups enough, 128-row tiles read each weight slab half as often)
-    if (a.M <= 4096 && (a.N < 16384 || a.M < 256)) {
-        if constexpr (sizeof(T) == 2) {
-            // Fewer 64 x 128 tiles than half the CUs (the fusion stack: 152-1328 tokens x 768 channels = 18-126 tiles): such a
-            // launch is a chain of K / 64 steps whose cost is the step's DMA issue (six 1-KB pieces per wave) plus a barrier, on a
-            // mostly idle GPU.  Quarter tiles (32 x 64) put four times the workgroups on the chip, each with half the pieces per
-            // wave and step.  Measured per launch inside a graph (tools/probes/few_probe.py, same call): 152-640 x 768 x 768 8.5 -> 5.5 us
-            // (hipBLASLt 7.5-8.1), 1328 x 768 x 768 9.2 -> 6.7, 664 x 1536 x 768 9.0 -> 6.5, 512 x 3072 x 768 12.9 -> 9.8,
-            // 512 x 768 x 3072 24.4 -> 16, 1328 x 768 x 3072 25.5 -> 19.5; with 256+ tiles of 64 x 128 the quarter tiles lose
-            // (1328 x 3072 x 768: 14 -> 22 us), and the four-buffer ring does nothing for K = 768.  (64 x 64 tiles: 6.4 us on the first group.)
-            constexpr int SMALL_TILES = 256;               // quarter tiles below this many 64 x 128 tiles
-            constexpr int SMALL_R4K = 2048;                // four-buffer ring from this K
-            const int tiles = ((a.M + 63) / 64) * ((a.N + 127) / 128);
-            if (tiles < SMALL_TILES && a.N % 64 == 0 && a.K % 64 == 0 && a.K >= 128 && !a.ksplit && a.ldx % 8 == 0 && a.ldw % 8 == 0) {
-                if (a.K >= SMALL_R4K) return launch_nt<T, 32, 64, 64, 4, true>(a, st, route);
-                return launch_nt<T, 32, 64, 64, 2, true>(a, st, route);
-            }
-        }
-        return n96 ? dispatch_nt_bk<T, 64, 96>(a, st, route) : dispatch_nt_bk<T, 64, 128>(a, st, route);
-    }
-    if constexpr (sizeof(T) == 2) {
-        int epi3 = 2;
-        if (const int ph = ph_plan(a, &epi3)) {
-            if (ph == 1) return launch_ph<2>(a, st, route);
-            if (ph == 4) return epi3 == 6 ? launch_ph3<6, true, 4>(a, st, route) : epi3 == 5 ? launch_ph3<5, true, 4>(a, st, route) : launch_ph3<2, true, 4>(a, st, route);
-            return epi3 == 3 ? launch_ph3<3>(a, st, route) : epi3 == 6 ? launch_ph3<6>(a, st, route) : epi3 == 5 ? launch_ph3<5>(a, st, route) : launch_ph3<2>(a, st, route);
-        }
-        if (const int bn = p256_plan(a))
-            return bn == 256 ? launch_p256<256, 64, 2>(a, st, route) : bn == 192 ? launch_p256<192, 64, 2>(a, st, route) : launch_p256<128, 64, 3>(a, st, route);
-        // measured (tools/probes/gemm_bench.py): +8 % on the 125440-token stage-2 shapes (K = 384: 496 -> 540 TF/s),
-        // -4 % on the 31360-token stage-3 shapes (tile quantisation at one workgroup per CU) -> only for M >= 65536
-        constexpr int DEEP_MINM = 65536, DEEP_MINK = 96;
-        // K = 96 (stage 0, three K steps): -5..7 % with the deep kernel except for the GELU + pre-activation launch
-        // (two output streams; measured +2 %), which keeps the single-step kernel
-        const bool big = a.M >= DEEP_MINM && !a.ksplit && a.K % 32 == 0 && a.K >= DEEP_MINK && a.ldx % 8 == 0 && a.ldw % 8 == 0 &&
-                         !(a.K == 96 && a.epi == FMMT_EPI_GELU);
-        if (big && (a.N % 128 == 0 || n96)) {
-            constexpr size_t lds = (size_t)3 * (256 + 128) * 64 * 2;
-            constexpr size_t lds96 = (size_t)3 * (256 + 96) * 32 * 2;
-            static FmmtLdsOnce lds_once[7];
-            if (!route) {
-                const void* fns[] = {reinterpret_cast<const void*>(&linear_nt_deep_kernel),
-                                     reinterpret_cast<const void*>(&linear_nt_deep32_kernel<0, 128>),
-                                     reinterpret_cast<const void*>(&linear_nt_deep32_kernel<6, 128>),
-                                     reinterpret_cast<const void*>(&linear_nt_deep32_kernel<3, 128>),
-                                     reinterpret_cast<const void*>(&linear_nt_deep32_kernel<0, 96>),
-                                     reinterpret_cast<const void*>(&linear_nt_deep32_kernel<6, 96>),
-                                     reinterpret_cast<const void*>(&linear_nt_deep32_kernel<3, 96>)};
-                const int sizes[] = {(int)lds, (int)lds / 2, (int)lds / 2, (int)lds / 2, (int)lds96, (int)lds96, (int)lds96};
-                for (int i = 0; i < 7; ++i)
-                    if (int rc_ = lds_once[i].set(fns[i], sizes[i])) return rc_;
-            }
-            LinArgs p = a;
-            p.tiles_m = (a.M + 255) / 256;
-            // one launch site per instantiation; with `route` set it names itself instead of launching
-#define FMMT_DEEP_LAUNCH(R, KERNEL, LDS) do { if (route) { *route = R; return 0; } hipLaunchKernelGGL(KERNEL, dim3(p.tiles_m * p.tiles_n), dim3(512), LDS, st, p); } while (0)
-            if (n96) {
-                p.tiles_n = a.N / 96;
-                if (a.K == 192) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K192_N96, (linear_nt_deep32_kernel<6, 96>), lds96);
-                else if (a.K == 96) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K96_N96, (linear_nt_deep32_kernel<3, 96>), lds96);
-                else FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_N96, (linear_nt_deep32_kernel<0, 96>), lds96);
-                FMMT_CHECK_LAUNCH();
-                return 0;
-            }
-            p.tiles_n = a.N / 128;
-            // measured (tools/probes/gemm_bench.py, 125440 tokens): the K-step-32 kernel with two workgroups per CU wins
-            // where the epilogue is a large share of a tile's life -- GELU / GELU' launches (0.388 -> 0.340 ms) and
-            // K = 384 (384x384: 0.069 -> 0.057 ms); the K-step-64 kernel keeps a 2-4 % edge on plain K >= 1152.
-            if (a.epi != 0 || a.K <= 512 || a.K % 64 != 0) {
-                if (a.K == 192) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K192_N128, (linear_nt_deep32_kernel<6, 128>), lds / 2);
-                else if (a.K == 96) FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_K96_N128, (linear_nt_deep32_kernel<3, 128>), lds / 2);
-                else FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP32_N128, (linear_nt_deep32_kernel<0, 128>), lds / 2);
-            } else {
-                FMMT_DEEP_LAUNCH(FMMT_ROUTE_DEEP, linear_nt_deep_kernel, lds);
-            }
-#undef FMMT_DEEP_LAUNCH
-            FMMT_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    // (256-row tiles with 4 waves measured: -30 % on the stage-2/3 shapes -- one workgroup per CU)
-    return n96 ? dispatch_nt_bk<T, 128, 96>(a, st, route) : dispatch_nt_bk<T, 128, 128>(a, st, route);
-}
+// gemm_ph.h / gemm_ph3.h keep launchers of their own (tools/probes/nt_ph_probe.hip calls them): they derive the tile counts themselves
+template <int EPI>
+int launch_ph_entry(const LinArgs& a, const GemmPlan&, hipStream_t st) { return launch_ph<EPI>(a, st); }
+template <int EPI, int WT>
+int launch_ph3_entry(const LinArgs& a, const GemmPlan&, hipStream_t st) { return launch_ph3<EPI, true, WT>(a, st); }
 
 // y = T(sum_s part[s] + bias) for the split-K path
 template <typename T>
@@ -1275,19 +1062,6 @@ __global__ void splitk_finish_kernel(const float* __restrict__ part, int splits,
     float t = bias ? bias[n] : 0.f;
     for (int s = 0; s < splits; ++s) t += part[(size_t)s * M * N + i];
     y[(size_t)m * ldy + n] = from_f32<T>(t);
-}
-
-// split-K plan for skinny problems (the 37632 -> 512 head): few output tiles, very long K
-int splitk_plan(int M, int N, int K, int* ksplit) {
-    const int bm = M <= 4096 ? 64 : 128;
-    const int tiles = ((M + bm - 1) / bm) * ((N + 127) / 128);
-    if (tiles >= 128 || K < 4096) { *ksplit = 0; return 1; }
-    int splits = 512 / tiles;
-    if (splits > 32) splits = 32;
-    int ks = (K + splits - 1) / splits;
-    ks = (ks + 63) / 64 * 64;
-    *ksplit = ks;
-    return (K + ks - 1) / ks;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1532,20 +1306,11 @@ void linear_tn_kernel(TnArgs p) {
 }
 
 template <typename T, int BMS, bool FEW = false, int PF = 1>
-int launch_tn(const TnArgs& a, dim3 grid, hipStream_t st, int* route) {
+int launch_tn(const TnArgs& a, const GemmPlan& pl, hipStream_t st) {
     constexpr int VEC = Vec<T>::N;
     constexpr size_t lds = (size_t)4 * BMS * (sizeof(T) == 2 ? 128 : 128 + VEC) * sizeof(T) + (256 / (128 / VEC)) * 128 * sizeof(float);
     static FmmtLdsOnce lds_once;
-    if (route) {
-        *route = sizeof(T) == 4 ? FMMT_ROUTE_TN_F32 : FEW ? FMMT_ROUTE_TN_REG32_FEW : BMS == 64 ? FMMT_ROUTE_TN_REG64 : FMMT_ROUTE_TN_REG32;
-        return 0;
-    }
-    if (lds > 65536) {
-        if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_kernel<T, BMS, FEW, PF>), (int)lds)) return rc_;
-    }
-    hipLaunchKernelGGL((linear_tn_kernel<T, BMS, FEW, PF>), grid, dim3(256), lds, st, a);
-    FMMT_CHECK_LAUNCH();
-    return 0;
+    return launch_once(&linear_tn_kernel<T, BMS, FEW, PF>, lds_once, lds, dim3(pl.grid), 256, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1683,22 +1448,9 @@ __global__ __launch_bounds__(512) void linear_tn_few_kernel(TnArgs p) {
     }
 }
 
-int launch_tn_few(int M, int N, int K, const void* dy, int lddy, const void* x, int ldx, float* dw, float* db, int* hdr, hipStream_t st, int* route) {
-    constexpr int lds = 80 * 1024;
+int launch_tn_few(const TnArgs& a, const GemmPlan& pl, hipStream_t st) {
     static FmmtLdsOnce lds_once;
-    if (route) { *route = FMMT_ROUTE_TN_FEW; return 0; }
-    if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_few_kernel), lds)) return rc_;
-    TnArgs a{M, N, K, dy, lddy, x, ldx, dw, db, nullptr, 1, K / 64, (M + 7) / 8, N / 64, 0, hdr, 1};
-    hipLaunchKernelGGL(linear_tn_few_kernel, dim3((N / 64) * (K / 64)), dim3(512), lds, st, a);
-    FMMT_CHECK_LAUNCH();
-    return 0;
-}
-
-// eligibility of linear_tn_few_kernel: bf16, 129..2048 tokens, whole 64 x 64 tiles, at least 8 of them, 16-byte rows
-bool tn_few_ok(int M, int N, int K, int dtype) {
-    // (at most 1024 tiles: the embedding head's 512 x 37632 gradient -- 4704 tiles of 640 tokens -- took 767 us here against 292 us
-    //  with the 128 x 128-tile kernel, whose workgroups reuse each staged token slab four times as often)
-    return dtype == FMMT_BF16 && M > 128 && M <= 2048 && N % 64 == 0 && K % 64 == 0 && (N / 64) * (K / 64) >= 8 && (N / 64) * (K / 64) <= 1024;
+    return launch_once(&linear_tn_few_kernel, lds_once, 80 * 1024, dim3(pl.grid), 512, st, a);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2110,19 +1862,11 @@ __global__ __launch_bounds__(512) void linear_tn_dma_kernel(TnArgs p) {
 }
 
 template <int TNn, int TKk, int NBUF, int WN, bool SCALED = false>
-int launch_tn_dma(const TnArgs& a, int grid, hipStream_t st, int* route) {
+int launch_tn_dma(const TnArgs& a, const GemmPlan& pl, hipStream_t st) {
     constexpr size_t lds = (size_t)NBUF * 32 * (TNn + TKk) * 2 + (SCALED ? 4096 + 64 : 0);
     static_assert(lds <= 160 * 1024, "LDS");
     static FmmtLdsOnce lds_once;
-    if (route) {
-        *route = TNn == 384 ? FMMT_ROUTE_TN_DMA_384 : TNn == 256 ? (SCALED ? FMMT_ROUTE_TN_DMA_256_SCALED : FMMT_ROUTE_TN_DMA_256)
-                                                                 : (SCALED ? FMMT_ROUTE_TN_DMA_192_SCALED : FMMT_ROUTE_TN_DMA_192);
-        return 0;
-    }
-    if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_tn_dma_kernel<TNn, TKk, NBUF, WN, SCALED>), (int)lds)) return rc_;
-    hipLaunchKernelGGL((linear_tn_dma_kernel<TNn, TKk, NBUF, WN, SCALED>), dim3(grid), dim3(512), lds, st, a);
-    FMMT_CHECK_LAUNCH();
-    return 0;
+    return launch_once(&linear_tn_dma_kernel<TNn, TKk, NBUF, WN, SCALED>, lds_once, lds, dim3(pl.grid), 512, st, a);
 }
 
 // out[i] = sum_s part[s][i] : 256 threads = 64 float4 outputs x 4 split groups, fixed-order tree (deterministic).
@@ -2191,68 +1935,96 @@ __global__ __launch_bounds__(64 * RP_GROUPS) void reduce_partials_kernel(const f
     }
 }
 
-struct TnPlan { int tiles_n, tiles_k, splits, chunk; size_t bytes; int tn, tk; int npad; };     // tn != 0: linear_tn_dma_kernel<tn>; npad: rows of a split's partials (0 = N)
-
-// (An XCD-local decomposition -- tile shapes 192 x 96 / 96 x 192 / 128 x 128 chosen so that all tiles of a token split fill
-//  whole XCDs, every dy / x slab fetched into exactly one L2 -- was written, tested and measured: the stage-2/3 launches of the
-//  step took 7.16 ms against 6.57 ms with this split-major order (same call).  The second fetch of a slab is served by the
-//  256 MB Infinity Cache; what the XCD-local form paid was 6-25 % idle workgroup slots and 244-252 registers.  Not kept.)
-TnPlan tn_plan(int M, int N, int K, int dtype) {
-    TnPlan pl;
-    pl.tn = pl.tk = 0;
-    pl.tiles_n = (N + 127) / 128;
-    pl.tiles_k = (K + 127) / 128;
-    const int tiles = pl.tiles_n * pl.tiles_k;
-    // one round of co-resident workgroups: 2 per CU for the 64-token-step kernels (64-78 KB LDS), 3 per CU for
-    // the 32-token-step kernel; more would run as a second, partly empty round
-    // (leaving head-room for the concurrent text-encoder stream -- 448/672, 384/576 -- measured: no gain)
-    const int target = (M <= 262144) ? 512 : 768;
-    int splits = target / tiles;
-    // few-token problems (fusion stack: 152-664 rows): one pass over the tokens per output tile, written straight to
-    // dW / db by fmmt_linear_wgrad -- a second launch to add two or three partials costs as much as the contraction
-    if (M <= 768) splits = 1;
-    const int max_by_rows = (M + 255) / 256;
-    if (splits > max_by_rows) splits = max_by_rows;
-    if (splits < 1) splits = 1;
-    // keep the partial buffer under 512 MiB
-    while (splits > 1 && (size_t)splits * N * K * 4 > ((size_t)512 << 20)) --splits;
-    int chunk = (M + splits - 1) / splits;
-    chunk = (chunk + 63) / 64 * 64;
-    pl.splits = (M + chunk - 1) / chunk;
-    pl.chunk = chunk;
-    pl.bytes = (size_t)pl.splits * ((size_t)N * K + N) * sizeof(float);
-    return pl;
+// The launch table: one entry per route of enum fmmt_route, exactly one of nt / tn set.
+struct Launch {
+    int (*nt)(const LinArgs&, const GemmPlan&, hipStream_t);
+    int (*tn)(const TnArgs&, const GemmPlan&, hipStream_t);
+};
+struct LaunchTable { Launch at[FMMT_ROUTE_COUNT]; };
+constexpr LaunchTable make_launch_table() {
+    LaunchTable t{};
+    t.at[FMMT_ROUTE_NT_QUARTER].nt = launch_nt<bf16, 32, 64, 64, 2, true>;
+    t.at[FMMT_ROUTE_NT_QUARTER_R4].nt = launch_nt<bf16, 32, 64, 64, 4, true>;
+    t.at[FMMT_ROUTE_NT_SEG3].nt = launch_nt<bf16, 32, 64, 64, 2, true, true>;
+    t.at[FMMT_ROUTE_NT_SEG3_R4].nt = launch_nt<bf16, 32, 64, 64, 4, true, true>;
+    t.at[FMMT_ROUTE_NT64_K96].nt = launch_nt_bn<bf16, 64, 96, 1>;
+    t.at[FMMT_ROUTE_NT64_K64].nt = launch_nt_bn<bf16, 64, 64, 1>;
+    t.at[FMMT_ROUTE_NT64_DMA].nt = launch_nt_bn<bf16, 64, 64, 2, true>;
+    t.at[FMMT_ROUTE_NT64_DMA_R4].nt = launch_nt_bn<bf16, 64, 64, 4, true>;
+    t.at[FMMT_ROUTE_NT64_BK64].nt = launch_nt_bn<bf16, 64, 64, 2>;
+    t.at[FMMT_ROUTE_NT64_BK32].nt = launch_nt_bn<bf16, 64, 32, 2>;
+    t.at[FMMT_ROUTE_NT64_F32].nt = launch_nt_bn<float, 64, 16, 2>;
+    t.at[FMMT_ROUTE_NT128_K96].nt = launch_nt_bn<bf16, 128, 96, 1>;
+    t.at[FMMT_ROUTE_NT128_K64].nt = launch_nt_bn<bf16, 128, 64, 1>;
+    t.at[FMMT_ROUTE_NT128_DMA].nt = launch_nt_bn<bf16, 128, 64, 2, true>;
+    t.at[FMMT_ROUTE_NT128_BK64].nt = launch_nt_bn<bf16, 128, 64, 2>;
+    t.at[FMMT_ROUTE_NT128_BK32].nt = launch_nt_bn<bf16, 128, 32, 2>;
+    t.at[FMMT_ROUTE_NT128_F32].nt = launch_nt_bn<float, 128, 16, 2>;
+    t.at[FMMT_ROUTE_PH].nt = launch_ph_entry<2>;
+    t.at[FMMT_ROUTE_PH3_PLAIN].nt = launch_ph3_entry<2, 2>;
+    t.at[FMMT_ROUTE_PH3_GELU_PRE].nt = launch_ph3_entry<3, 2>;
+    t.at[FMMT_ROUTE_PH3_OP].nt = launch_ph3_entry<5, 2>;
+    t.at[FMMT_ROUTE_PH3_MUL_AUX].nt = launch_ph3_entry<6, 2>;
+    t.at[FMMT_ROUTE_PH3W_PLAIN].nt = launch_ph3_entry<2, 4>;
+    t.at[FMMT_ROUTE_PH3W_OP].nt = launch_ph3_entry<5, 4>;
+    t.at[FMMT_ROUTE_PH3W_MUL_AUX].nt = launch_ph3_entry<6, 4>;
+    t.at[FMMT_ROUTE_P256_256].nt = launch_p256_b<256, 64, 2, true, false>;
+    t.at[FMMT_ROUTE_P256_256_PIPE].nt = launch_p256_b<256, 64, 2, true, false, true>;
+    t.at[FMMT_ROUTE_P256_192].nt = launch_p256_b<192, 64, 2, true, false>;
+    t.at[FMMT_ROUTE_P256_192_PIPE].nt = launch_p256_b<192, 64, 2, true, false, true>;
+    t.at[FMMT_ROUTE_P256_192_OP].nt = launch_p256_b<192, 64, 2, true, true>;
+    t.at[FMMT_ROUTE_P256_128].nt = launch_p256_b<128, 64, 3, true, false>;
+    t.at[FMMT_ROUTE_P256_128_PIPE].nt = launch_p256_b<128, 64, 3, true, false, true>;
+    t.at[FMMT_ROUTE_P256_128_OP].nt = launch_p256_b<128, 64, 3, true, true>;
+    t.at[FMMT_ROUTE_DEEP32_K96_N96].nt = launch_deep32<3, 96>;
+    t.at[FMMT_ROUTE_DEEP32_K192_N96].nt = launch_deep32<6, 96>;
+    t.at[FMMT_ROUTE_DEEP32_N96].nt = launch_deep32<0, 96>;
+    t.at[FMMT_ROUTE_DEEP32_K96_N128].nt = launch_deep32<3, 128>;
+    t.at[FMMT_ROUTE_DEEP32_K192_N128].nt = launch_deep32<6, 128>;
+    t.at[FMMT_ROUTE_DEEP32_N128].nt = launch_deep32<0, 128>;
+    t.at[FMMT_ROUTE_DEEP].nt = launch_deep;
+    t.at[FMMT_ROUTE_TN_FEW].tn = launch_tn_few;
+    t.at[FMMT_ROUTE_TN_REG32_FEW].tn = launch_tn<bf16, 32, true>;
+    t.at[FMMT_ROUTE_TN_REG64].tn = launch_tn<bf16, 64, false, 2>;
+    t.at[FMMT_ROUTE_TN_REG32].tn = launch_tn<bf16, 32, false, 2>;
+    t.at[FMMT_ROUTE_TN_F32].tn = launch_tn<float, 16>;
+    t.at[FMMT_ROUTE_TN_DMA_256].tn = launch_tn_dma<256, 256, 4, 2>;
+    t.at[FMMT_ROUTE_TN_DMA_192].tn = launch_tn_dma<192, 384, 4, 2>;
+    t.at[FMMT_ROUTE_TN_DMA_384].tn = launch_tn_dma<384, 192, 4, 4>;
+    t.at[FMMT_ROUTE_TN_DMA_256_SCALED].tn = launch_tn_dma<256, 256, 4, 2, true>;
+    t.at[FMMT_ROUTE_TN_DMA_192_SCALED].tn = launch_tn_dma<192, 384, 4, 2, true>;
+    return t;
 }
+constexpr LaunchTable LAUNCH = make_launch_table();
+constexpr int launch_entries() {
+    int n = 0;
+    for (int r = 1; r < FMMT_ROUTE_COUNT; ++r) n += (LAUNCH.at[r].nt != nullptr) != (LAUNCH.at[r].tn != nullptr);
+    return n;
+}
+static_assert(launch_entries() == FMMT_ROUTE_COUNT - 1, "every route of enum fmmt_route has exactly one launcher");
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// The entry points' bodies take `int* route` (include/fmmt_route.h): NULL launches; non-NULL runs the same validation and dispatch and stores the
-// FMMT_ROUTE_* value at the place where the launch would be issued -- no HIP call on that path.
-
-// Every epilogue moves 16-byte vectors at row * ld + column (nt_epilogue / _slab / _wslab, the p256 slab stores, the buffer stores of gemm_ph.h /
-// gemm_ph3.h; DESIGN.md "Leading dimensions of the GEMMs"): N and every ld of a present M x N operand keep each row 16-byte aligned.
-int linear_fwd_impl(int dtype, int M, int N, int K,
-                    const void* x, int ldx, const void* w, int ldw, const float* bias,
-                    void* y, int ldy, void* y_pre,
-                    int epi, const void* aux, int ldaux,
-                    const void* res, int ldres, const float* rowscale, int rows_per_scale,
-                    void* stream, int* route) {
-    if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
-    const int vec = dtype == FMMT_BF16 ? 8 : 4;
-    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
-    if (K % vec || N % vec || ldx % vec || ldw % vec || ldy % vec) return FMMT_EINVAL;
-    if (ldx < K || ldw < K || ldy < N) return FMMT_EINVAL;
-    if (epi < 0 || epi > FMMT_EPI_MUL_AUX) return FMMT_EINVAL;
-    if ((epi == FMMT_EPI_GELU_BWD || epi == FMMT_EPI_MUL_AUX) && !aux) return FMMT_EINVAL;
-    if (aux && (ldaux % vec || ldaux < N)) return FMMT_EINVAL;
-    if (res && (ldres % vec || ldres < N)) return FMMT_EINVAL;
-    if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
-    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (bias && !aligned16(bias)) ||
-        (res && !aligned16(res)) || (aux && !aligned16(aux)) || (y_pre && !aligned16(y_pre)))
-        return FMMT_EALIGN;
-    LinArgs a{M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, 0, 0, 0, 0, nullptr};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st, route) : dispatch_nt<float>(a, st, route);
+// The contraction of fmmt_linear_wgrad / _partials.  *direct: it wrote dw / db themselves (fmmt_linear_wgrad, one split); otherwise the partials lie in
+// the workspace as the plan carves it, part_w [splits][rows][K], part_b [splits][rows] (left out without want_bias).  One TnArgs for every TN route:
+// FMMT_ROUTE_TN_FEW is planned only without a rowscale, and linear_tn_few_kernel reads neither rowscale nor rows_per_scale.
+int wgrad_contract(const GemmQuery& q, const void* dy, const void* x, float* dw, float* db, int want_bias, const float* rowscale,
+                   void* workspace, size_t workspace_bytes, void* stream, bool* direct) {
+    if (int rc = check_query(q)) return rc;
+    const GemmPlan pl = plan_query(q);
+    *direct = pl.direct;
+    if (!aligned16(dy) || !aligned16(x) || (!pl.direct && !aligned16(workspace))) return FMMT_EALIGN;
+    if (!pl.direct && workspace_bytes < pl.ws_bytes) return FMMT_EWORKSPACE;
+    if (pl.route < 0) return pl.route;
+    int* const hdr = pl.direct ? nullptr : reinterpret_cast<int*>(workspace);
+    float* const part_b = pl.direct ? db : reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + TN_HDR);
+    float* const part_w = pl.direct ? dw : part_b + (size_t)pl.smax * pl.rows;
+    const TnArgs a{q.M, q.N, q.K, dy, q.ldy, x, q.ldx, part_w, pl.direct || want_bias ? part_b : nullptr, rowscale, q.rows_per_scale,
+                   pl.tiles_k, pl.chunk, pl.tiles_n, q.x_epi == FMMT_EPI_GELU, hdr, pl.splits, pl.npad};
+    return LAUNCH.at[pl.route].tn(a, pl, reinterpret_cast<hipStream_t>(stream));
+}
+GemmQuery wgrad_query(int mode, int dtype, int M, int N, int K, int lddy, int ldx, bool rowscale, int rows_per_scale, int x_epi) {
+    return GemmQuery{mode, dtype, M, N, K, ldx, 0, lddy, 0, 0, false, false, false, false, rowscale, 0, rows_per_scale, x_epi};
 }
 
 }  // namespace
@@ -2263,301 +2035,116 @@ extern "C" int fmmt_linear_fwd(int dtype, int M, int N, int K,
                                int epi, const void* aux, int ldaux,
                                const void* res, int ldres, const float* rowscale, int rows_per_scale,
                                void* stream) {
-    return linear_fwd_impl(dtype, M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, stream, nullptr);
+    const GemmQuery q{GEMM_FWD, dtype, M, N, K, ldx, ldw, ldy, ldaux, ldres, bias != nullptr, y_pre != nullptr, aux != nullptr, res != nullptr, rowscale != nullptr,
+                      epi, rows_per_scale, 0};
+    if (int rc = check_query(q)) return rc;
+    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || (bias && !aligned16(bias)) ||
+        (res && !aligned16(res)) || (aux && !aligned16(aux)) || (y_pre && !aligned16(y_pre)))
+        return FMMT_EALIGN;
+    const GemmPlan pl = plan_query(q);
+    if (pl.route < 0) return pl.route;
+    const LinArgs a{M, N, K, x, ldx, w, ldw, bias, y, ldy, y_pre, epi, aux, ldaux, res, ldres, rowscale, rows_per_scale, 0, 0, 0, 0, nullptr};
+    return LAUNCH.at[pl.route].nt(a, pl, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Few-token Linear over THREE weights in one launch (MELDTransEncoder's query / key / value, modules/Transformer.py:64-103: three nn.Linear over
 // the same hidden states, and their input gradient dx = dq Wq + dk Wk + dv Wv).
 //   seg_mode 1 (along N): y[:, s * N/3 : (s + 1) * N/3] = x @ w_s^T + bias_s        w_s [N/3][K]
 //   seg_mode 2 (along K): y = sum_s x[:, s * K/3 : (s + 1) * K/3] @ w_s^T            w_s [N][K/3]   (no bias)
-// bf16, the direct-to-LDS quarter-tile kernels only (the shapes dispatch_nt sends there: tokens <= 4096, few tiles); anything else: FMMT_EINVAL and
-// the caller issues three fmmt_linear_fwd calls.
-namespace {
-int seg_mode_cols(int seg_mode, int K) { return seg_mode == 2 ? K / 3 : K; }   // row width of one of the three weights
-int linear_fwd_seg3_impl(int dtype, int M, int N, int K, const void* x, int ldx, const void* w0, const void* w1, const void* w2, int ldw,
-                         int seg_mode, const float* bias0, const float* bias1, const float* bias2, void* y, int ldy, void* stream, int* route) {
-    if (dtype != FMMT_BF16 || M <= 0 || N <= 0 || K <= 0 || (seg_mode != 1 && seg_mode != 2)) return FMMT_EINVAL;
-    if (!x || !w0 || !w1 || !w2 || !y) return FMMT_EINVAL;
-    const int seg = seg_mode == 1 ? N / 3 : K / 3;
-    if ((seg_mode == 1 ? N : K) % 3 || seg % 64 || N % 64 || K % 64 || K < 128 || ldx % 8 || ldw % 8 || ldy % 8 || M > 4096) return FMMT_EINVAL;
-    if (ldx < K || ldw < seg_mode_cols(seg_mode, K) || ldy < N) return FMMT_EINVAL;
-    if (seg_mode == 2 && (bias0 || bias1 || bias2)) return FMMT_EINVAL;
-    if (!aligned16(x) || !aligned16(w0) || !aligned16(w1) || !aligned16(w2) || !aligned16(y)) return FMMT_EALIGN;
-    if (((M + 63) / 64) * ((N + 127) / 128) >= 256) return FMMT_EINVAL;                 // dispatch_nt's few-tile rule: larger problems do not come here
-    LinArgs a{M, N, K, x, ldx, w0, ldw, bias0, y, ldy, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, 0, nullptr};
-    a.w1 = w1;
-    a.w2 = w2;
-    a.bias1 = bias1;
-    a.bias2 = bias2;
-    a.wseg = seg;
-    a.wseg_mode = seg_mode;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (K >= 2048) return launch_nt<bf16, 32, 64, 64, 4, true, true>(a, st, route);
-    return launch_nt<bf16, 32, 64, 64, 2, true, true>(a, st, route);
-}
-}  // namespace
-
+// What it refuses (check_query, plan_query) the caller issues as three fmmt_linear_fwd calls.
 extern "C" int fmmt_linear_fwd_seg3(int dtype, int M, int N, int K, const void* x, int ldx, const void* w0, const void* w1, const void* w2, int ldw,
                                     int seg_mode, const float* bias0, const float* bias1, const float* bias2, void* y, int ldy, void* stream) {
-    return linear_fwd_seg3_impl(dtype, M, N, K, x, ldx, w0, w1, w2, ldw, seg_mode, bias0, bias1, bias2, y, ldy, stream, nullptr);
+    if ((seg_mode != 1 && seg_mode != 2) || !x || !w0 || !w1 || !w2 || !y) return FMMT_EINVAL;
+    const GemmQuery q{seg_mode == 1 ? GEMM_SEG3_N : GEMM_SEG3_K, dtype, M, N, K, ldx, ldw, ldy, 0, 0, bias0 || bias1 || bias2, false, false, false, false, 0, 1, 0};
+    if (int rc = check_query(q)) return rc;
+    if (!aligned16(x) || !aligned16(w0) || !aligned16(w1) || !aligned16(w2) || !aligned16(y)) return FMMT_EALIGN;
+    const GemmPlan pl = plan_query(q);
+    if (pl.route < 0) return pl.route;
+    const LinArgs a{M, N, K, x, ldx, w0, ldw, bias0, y, ldy, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, 0, nullptr,
+                    w1, w2, bias1, bias2, seg_mode == 1 ? N / 3 : K / 3, seg_mode};
+    return LAUNCH.at[pl.route].nt(a, pl, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" size_t fmmt_linear_splitk_workspace(int M, int N, int K) {
-    int ks;
-    const int splits = splitk_plan(M, N, K, &ks);
-    return ks ? (size_t)splits * M * N * sizeof(float) : 0;
-}
-
-namespace {
-int linear_fwd_splitk_impl(int dtype, int M, int N, int K, const void* x, int ldx, const void* w, int ldw,
-                           const float* bias, void* y, int ldy, void* workspace, size_t workspace_bytes,
-                           void* stream, int* route) {
-    if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
-    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
-    const int vec = dtype == FMMT_BF16 ? 8 : 4;
-    // the finish kernel stores single elements at m * ldy + n and the partials are f32x4 at m * N + n: any N % 4 and any pitch that holds a row
-    // would be addressable; N and ldy are held to fmmt_linear_fwd's rule (% 8 in bf16) so that one shape and one output view serve both entry points
-    if (K % vec || N % vec || ldx % vec || ldw % vec) return FMMT_EINVAL;
-    if (!y || ldy < N || ldy % vec || ldx < K || ldw < K) return FMMT_EINVAL;
-    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || !aligned16(workspace)) return FMMT_EALIGN;
-    int ks;
-    const int splits = splitk_plan(M, N, K, &ks);
-    if (!ks) return FMMT_EINVAL;                            // not a split-K shape: use fmmt_linear_fwd
-    if (workspace_bytes < (size_t)splits * M * N * sizeof(float)) return FMMT_EWORKSPACE;
-    LinArgs a{M, N, K, x, ldx, w, ldw, nullptr, nullptr, N, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, ks,
-              reinterpret_cast<float*>(workspace)};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (int rc = (dtype == FMMT_BF16 ? dispatch_nt<bf16>(a, st, route) : dispatch_nt<float>(a, st, route))) return rc;
-    if (route) return 0;                                   // the contraction's route; the finish below is one kernel for every shape
-    const size_t total = (size_t)M * N;
-    if (dtype == FMMT_BF16)
-        hipLaunchKernelGGL(splitk_finish_kernel<bf16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, splits, M, N, bias, (bf16*)y, ldy);
-    else
-        hipLaunchKernelGGL(splitk_finish_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, splits, M, N, bias, (float*)y, ldy);
-    FMMT_CHECK_LAUNCH();
-    return 0;
-}
-}  // namespace
+extern "C" size_t fmmt_linear_splitk_workspace(int M, int N, int K) { return plan_query(GemmQuery{GEMM_SPLITK, FMMT_BF16, M, N, K, K, K, N}).ws_bytes; }
 
 extern "C" int fmmt_linear_fwd_splitk(int dtype, int M, int N, int K, const void* x, int ldx, const void* w, int ldw,
                                       const float* bias, void* y, int ldy, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    return linear_fwd_splitk_impl(dtype, M, N, K, x, ldx, w, ldw, bias, y, ldy, workspace, workspace_bytes, stream, nullptr);
+    // the finish kernel stores single elements at m * ldy + n and the partials are f32x4 at m * N + n: any N % 4 and any pitch that holds a row
+    // would be addressable; N and ldy are held to fmmt_linear_fwd's rule (% 8 in bf16) so that one shape and one output view serve both entry points
+    const GemmQuery q{GEMM_SPLITK, dtype, M, N, K, ldx, ldw, ldy, 0, 0, bias != nullptr, false, false, false, false, 0, 1, 0};
+    if (!y) return FMMT_EINVAL;
+    if (int rc = check_query(q)) return rc;
+    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || !aligned16(workspace)) return FMMT_EALIGN;
+    const GemmPlan pl = plan_query(q);
+    if (pl.route < 0) return pl.route;
+    if (workspace_bytes < pl.ws_bytes) return FMMT_EWORKSPACE;
+    const LinArgs a{M, N, K, x, ldx, w, ldw, nullptr, nullptr, N, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 1, 0, 0, 0, pl.ksplit,
+                    reinterpret_cast<float*>(workspace)};
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (int rc = LAUNCH.at[pl.route].nt(a, pl, st)) return rc;
+    const size_t total = (size_t)M * N;
+    if (dtype == FMMT_BF16)
+        hipLaunchKernelGGL(splitk_finish_kernel<bf16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, pl.splits, M, N, bias, (bf16*)y, ldy);
+    else
+        hipLaunchKernelGGL(splitk_finish_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a.part, pl.splits, M, N, bias, (float*)y, ldy);
+    FMMT_CHECK_LAUNCH();
+    return 0;
 }
 
-// fake operands of the route queries: present, 16-byte aligned, never dereferenced (no launch is issued with `route` set)
-namespace {
-void* route_ptr(int present) { return present ? reinterpret_cast<void*>(static_cast<uintptr_t>(4096)) : nullptr; }
-}  // namespace
-
+// The route queries (include/fmmt_route.h): the entry points' own check_query() and plan_query() on the same query, pointers as presence flags
+// (present ones count as 16-byte aligned, workspaces as large enough); the answer is the index the entry point would take into LAUNCH.
 extern "C" int fmmt_linear_fwd_route(int dtype, int M, int N, int K, int ldx, int ldw, int ldy, int has_bias, int has_y_pre, int epi,
                                      int has_aux, int ldaux, int has_res, int ldres, int has_rowscale, int rows_per_scale, int mode) {
-    int route = 0, rc;
-    void* const pp = route_ptr(1);
-    const float* const bias = reinterpret_cast<const float*>(route_ptr(has_bias));
-    if (mode == FMMT_ROUTE_MODE_FWD)
-        rc = linear_fwd_impl(dtype, M, N, K, pp, ldx, pp, ldw, bias, pp, ldy, route_ptr(has_y_pre), epi, route_ptr(has_aux), ldaux, route_ptr(has_res), ldres,
-                             reinterpret_cast<const float*>(route_ptr(has_rowscale)), rows_per_scale, nullptr, &route);
-    else if (mode == FMMT_ROUTE_MODE_SEG3_N || mode == FMMT_ROUTE_MODE_SEG3_K)
-        rc = linear_fwd_seg3_impl(dtype, M, N, K, pp, ldx, pp, pp, pp, ldw, mode, bias, bias, bias, pp, ldy, nullptr, &route);
-    else if (mode == FMMT_ROUTE_MODE_SPLITK)
-        rc = linear_fwd_splitk_impl(dtype, M, N, K, pp, ldx, pp, ldw, bias, pp, ldy, pp, ~(size_t)0, nullptr, &route);
-    else
-        return FMMT_EINVAL;
-    return rc ? rc : route;
+    if (mode < FMMT_ROUTE_MODE_FWD || mode > FMMT_ROUTE_MODE_SPLITK) return FMMT_EINVAL;
+    return route_of(GemmQuery{mode, dtype, M, N, K, ldx, ldw, ldy, ldaux, ldres, has_bias != 0, has_y_pre != 0, has_aux != 0, has_res != 0, has_rowscale != 0,
+                              epi, rows_per_scale, 0});
 }
-
-namespace {
-// DMA-staged plan (linear_tn_dma_kernel): tile TNn x 128 with TNn = 256 / 192, one workgroup per CU, splits = 256 / tiles
-TnPlan tn_plan_dma(int M, int N, int K) {
-    TnPlan pl{0, 0, 0, 0, 0, 0, 0, 0};
-    // History: the first version of this kernel (256 / 192 x 128 tiles,
-    // the builtin ds_read_tr) measured 3-9 % SLOWER than the register-staged kernel with 68 % of its wave cycles parked in
-    // waits -- hipcc had put s_waitcnt vmcnt(0) in front of every stage's first fragment read, so the ring never had a second
-    // stage in flight.  With the reads in inline asm, 128 FLOP per staged byte and four 32-token stages: 860-1105 TF/s against
-    // 550-630.
-    // Fewest tokens for this kernel, exclusive.  8192 since the 320-frame legs (configs[4]: 15680 stage-3 tokens)
-    // measured 56.2 -> 55.7 ms per step with it, three alternating pairs in one call; 16384 before.
-    constexpr int TN_DMA_MINM = 8192;
-    if (M <= TN_DMA_MINM || M % 64) return pl;
-    int tn = 0, tk = 0;
-    if (N % 256 == 0 && K % 256 == 0) tn = 256, tk = 256;
-    else if (N % 192 == 0 && K % 384 == 0) tn = 192, tk = 384;
-    // round 6: the transposed tile for K = 192 (Swin stage 1's fc1 weight gradient, 768 x 192: it fell to the 128 x 128 register-staged kernel at 3.3 TB/s
-    // where its mirror image 192 x 768 runs at 4.7 on <192,384>); one k-tile only (the bias blocks' positions assume it), unscaled launches only
-    // N = 576 (stage 1's qkv weight gradient) is 192 short of two tiles: the last tile's upper half re-reads valid columns and its products go to partial rows
-    // the finish pass drops (npad)
-    else if ((N % 384 == 0 || (N % 384 == 192 && N >= 576)) && K == 192) tn = 384, tk = 192;
-    // (two or three tiles used to be refused -- > 64 splits, "the partial sums outweigh the operands" --; re-measured in round 4, same call:
-    //  501760 x 192 x 768 with the DropPath scale 324 -> 233 us, 125440 x 384 x 384 70 -> 64 us with the finish pass, no shape slower.  One tile stays out.)
-    const int npad = tn ? (N + tn - 1) / tn * tn : 0;
-    if (tn && (npad / tn) * (K / tk) < 2) tn = 0;
-    if (!tn) return pl;
-    const int tiles = (npad / tn) * (K / tk);
-    if (tiles > 128) return pl;
-    int splits = 256 / tiles;
-    while (splits > 1 && (size_t)splits * npad * K * 4 > ((size_t)512 << 20)) --splits;
-    int chunk = (M + splits - 1) / splits;
-    chunk = (chunk + 63) / 64 * 64;
-    splits = (M + chunk - 1) / chunk;
-    if (chunk < 512) return pl;
-    pl = TnPlan{npad / tn, K / tk, splits, chunk, 0, tn, tk, npad == N ? 0 : npad};
-    return pl;
-}
-
-// Workspace: [256-byte header | bias partials smax x N | weight partials smax x N x K], smax = the larger split count of the
-// plans a (dtype, M, N, K) launch may take.  Which plan a launch takes also depends on its operands (DropPath scale ...), so
-// the contraction kernel records the split count it wrote in the header and the finish pass reads it from there.
-constexpr size_t TN_HDR = 256;
-int tn_smax(int M, int N, int K, int dtype) {
-    int smax = tn_plan(M, N, K, dtype).splits;
-    if (dtype == FMMT_BF16) {
-        const TnPlan pd = tn_plan_dma(M, N, K);
-        if (pd.tn && pd.splits > smax) smax = pd.splits;
-    }
-    return smax;
-}
-// rows of a split's partials the workspace is carved for: N, or the padded count of a DMA plan that may take the launch
-int tn_rows(int M, int N, int K, int dtype) {
-    if (dtype == FMMT_BF16) {
-        const TnPlan pd = tn_plan_dma(M, N, K);
-        if (pd.tn && pd.npad > N) return pd.npad;
-    }
-    return N;
-}
-size_t tn_ws_bytes(int M, int N, int K, int dtype) {
-    const size_t rows = (size_t)tn_rows(M, N, K, dtype);
-    return TN_HDR + (size_t)tn_smax(M, N, K, dtype) * (rows * K + rows) * sizeof(float);
-}
-
-}  // namespace
 
 extern "C" size_t fmmt_linear_wgrad_workspace(int dtype, int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0 || (dtype != FMMT_BF16 && dtype != FMMT_F32)) return 0;
-    return tn_ws_bytes(M, N, K, dtype);
+    return launch_tn_plan(wgrad_query(GEMM_WGRAD_PARTIALS, dtype, M, N, K, N, K, false, 1, 0)).ws_bytes;
 }
-
-namespace {
-// the split contraction: part_w [splits][N][K], part_b [splits][N] or nullptr (splits == 1: these may be dw / db themselves)
-int launch_tn_plan(int dtype, int M, int N, int K, const void* dy, int lddy, const void* x, int ldx, float* part_w, float* part_b,
-                   const float* rowscale, int rows_per_scale, int x_epi, int* hdr, hipStream_t st, int* route) {
-    if (x_epi != 0 && x_epi != FMMT_EPI_GELU) return FMMT_EINVAL;
-    if (tn_few_ok(M, N, K, dtype) && !rowscale && !x_epi && lddy % 8 == 0 && ldx % 8 == 0)
-        return launch_tn_few(M, N, K, dy, lddy, x, ldx, part_w, part_b, hdr, st, route);     // one split: part_w / part_b may be dw / db themselves
-    if (dtype == FMMT_BF16 && hdr && !x_epi && lddy % 8 == 0 && ldx % 8 == 0) {
-        const TnPlan pd = tn_plan_dma(M, N, K);
-        // scaled launches: the split's slice of the scale vector has to fit the 4 KB behind the ring
-        const bool scaled_ok = !rowscale || (rows_per_scale >= 32 && pd.tn && pd.tk != 192 && pd.chunk / rows_per_scale + 2 <= 1024);
-        if (pd.tn && scaled_ok) {
-            TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pd.tiles_k, pd.chunk, pd.tiles_n, 0, hdr, pd.splits, pd.npad};
-            const int grid = pd.tiles_n * pd.tiles_k * pd.splits;
-            if (rowscale) return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2, true>(a, grid, st, route) : launch_tn_dma<192, 384, 4, 2, true>(a, grid, st, route);
-            if (pd.tk == 192) return launch_tn_dma<384, 192, 4, 4>(a, grid, st, route);
-            return pd.tk == 256 ? launch_tn_dma<256, 256, 4, 2>(a, grid, st, route) : launch_tn_dma<192, 384, 4, 2>(a, grid, st, route);
-        }
-    }
-    const TnPlan pl = tn_plan(M, N, K, dtype);
-    TnArgs a{M, N, K, dy, lddy, x, ldx, part_w, part_b, rowscale, rows_per_scale, pl.tiles_k, pl.chunk, pl.tiles_n, x_epi == FMMT_EPI_GELU, hdr, pl.splits};
-    dim3 grid(pl.tiles_n * pl.tiles_k * pl.splits);
-    if (dtype == FMMT_BF16) {
-        if (M <= 4096) return launch_tn<bf16, 32, true>(a, grid, st, route);      // few-token problems: 32-token steps, one in flight
-        // measured (tools/probes/gemm_bench.py): 64-token steps win for the compute-heavy stage-2/3 shapes (+15-25 %),
-        // 32-token steps (3 workgroups per CU) win for the HBM-bound multi-million-token stage-0/1 shapes.
-        // Two token steps in flight (register sets R0/R1): measured +3..5 % on the stage-2/3 shapes, +3..11 % on the stage-0/1
-        // ones, at unchanged occupancy (200 / 160 registers)
-        if (M <= 262144) return launch_tn<bf16, 64, false, 2>(a, grid, st, route);
-        return launch_tn<bf16, 32, false, 2>(a, grid, st, route);
-    }
-    return launch_tn<float, 16>(a, grid, st, route);
-}
-}  // namespace
-
-namespace {
-int linear_wgrad_partials_impl(int dtype, int M, int N, int K,
-                               const void* dy, int lddy, const void* x, int ldx, int want_bias,
-                               const float* rowscale, int rows_per_scale, int x_epi,
-                               void* workspace, size_t workspace_bytes, void* stream, int* route) {
-    if (M <= 0 || N <= 0 || K <= 0) return FMMT_EINVAL;
-    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
-    const int vec = dtype == FMMT_BF16 ? 8 : 4;
-    if (N % vec || K % vec || lddy % vec || ldx % vec || lddy < N || ldx < K) return FMMT_EINVAL;
-    if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
-    if (!aligned16(dy) || !aligned16(x) || !aligned16(workspace)) return FMMT_EALIGN;
-    if (workspace_bytes < tn_ws_bytes(M, N, K, dtype)) return FMMT_EWORKSPACE;
-    const int smax = tn_smax(M, N, K, dtype);
-    int* hdr = reinterpret_cast<int*>(workspace);
-    float* part_b = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + TN_HDR);
-    float* part_w = part_b + (size_t)smax * tn_rows(M, N, K, dtype);
-    return launch_tn_plan(dtype, M, N, K, dy, lddy, x, ldx, part_w, want_bias ? part_b : nullptr, rowscale, rows_per_scale, x_epi, hdr,
-                          reinterpret_cast<hipStream_t>(stream), route);
-}
-}  // namespace
 
 extern "C" int fmmt_linear_wgrad_partials(int dtype, int M, int N, int K,
                                           const void* dy, int lddy, const void* x, int ldx, int want_bias,
                                           const float* rowscale, int rows_per_scale, int x_epi,
                                           void* workspace, size_t workspace_bytes, void* stream) {
-    return linear_wgrad_partials_impl(dtype, M, N, K, dy, lddy, x, ldx, want_bias, rowscale, rows_per_scale, x_epi, workspace, workspace_bytes, stream, nullptr);
+    bool direct;
+    return wgrad_contract(wgrad_query(GEMM_WGRAD_PARTIALS, dtype, M, N, K, lddy, ldx, rowscale != nullptr, rows_per_scale, x_epi), dy, x, nullptr, nullptr, want_bias,
+                          rowscale, workspace, workspace_bytes, stream, &direct);
 }
 
 extern "C" int fmmt_linear_wgrad_finish(int dtype, int M, int N, int K, float* dw, float* db,
                                         const void* workspace, size_t workspace_bytes, void* stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || !dw) return FMMT_EINVAL;
-    if (dtype != FMMT_BF16 && dtype != FMMT_F32) return FMMT_EINVAL;
+    if (M <= 0 || N <= 0 || K <= 0 || !dw || (dtype != FMMT_BF16 && dtype != FMMT_F32)) return FMMT_EINVAL;
     if (!aligned16(dw) || !aligned16(workspace)) return FMMT_EALIGN;
-    if (workspace_bytes < tn_ws_bytes(M, N, K, dtype)) return FMMT_EWORKSPACE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int smax = tn_smax(M, N, K, dtype);
+    const GemmPlan pl = launch_tn_plan(wgrad_query(GEMM_WGRAD_PARTIALS, dtype, M, N, K, N, K, false, 1, 0));      // the carving: (dtype, M, N, K) alone
+    if (workspace_bytes < pl.ws_bytes) return FMMT_EWORKSPACE;
     const int* hdr = reinterpret_cast<const int*>(workspace);
     const float* part_b = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + TN_HDR);
-    const int rows = tn_rows(M, N, K, dtype);                // >= N: the grid covers the padded partials, the kernel reads the row count actually written from the header
-    const float* part_w = part_b + (size_t)smax * rows;
+    const int rows = pl.rows;                                // >= N: the grid covers the padded partials, the kernel reads the row count actually written from the header
+    const float* part_w = part_b + (size_t)pl.smax * rows;
     const size_t nw = (size_t)N * K;
     if (nw % 4 || N % 4) return FMMT_EINVAL;
     const int wblocks = (int)(((size_t)rows * K / 4 + 63) / 64), bblocks = db ? (rows / 4 + 63) / 64 : 0;
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(wblocks + bblocks), dim3(64 * RP_GROUPS), 0, st, part_w, dw, nw, hdr, wblocks, part_b, db, (size_t)N, K);
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(wblocks + bblocks), dim3(64 * RP_GROUPS), 0, reinterpret_cast<hipStream_t>(stream), part_w, dw, nw, hdr, wblocks, part_b, db, (size_t)N, K);
     FMMT_CHECK_LAUNCH();
     return 0;
 }
-
-namespace {
-int linear_wgrad_impl(int dtype, int M, int N, int K,
-                      const void* dy, int lddy, const void* x, int ldx,
-                      float* dw, float* db, const float* rowscale, int rows_per_scale, int x_epi,
-                      void* workspace, size_t workspace_bytes, void* stream, int* route) {
-    if (!aligned16(dw)) return FMMT_EALIGN;
-    const bool few = M > 0 && N > 0 && K > 0 && tn_few_ok(M, N, K, dtype) && !rowscale && !x_epi && lddy % 8 == 0 && ldx % 8 == 0;
-    if (M > 0 && N > 0 && K > 0 && (dtype == FMMT_BF16 || dtype == FMMT_F32) && (few || tn_smax(M, N, K, dtype) == 1)) {
-        // single split: the "partials" ARE the result -- let the contraction kernel write dw / db directly
-        const int vec = dtype == FMMT_BF16 ? 8 : 4;
-        if (N % vec || K % vec || lddy % vec || ldx % vec || lddy < N || ldx < K) return FMMT_EINVAL;
-        if (rowscale && rows_per_scale <= 0) return FMMT_EINVAL;
-        if (!aligned16(dy) || !aligned16(x)) return FMMT_EALIGN;
-        return launch_tn_plan(dtype, M, N, K, dy, lddy, x, ldx, dw, db, rowscale, rows_per_scale, x_epi, nullptr, reinterpret_cast<hipStream_t>(stream), route);
-    }
-    if (int rc = linear_wgrad_partials_impl(dtype, M, N, K, dy, lddy, x, ldx, db != nullptr, rowscale, rows_per_scale, x_epi,
-                                            workspace, workspace_bytes, stream, route)) return rc;
-    if (route) return 0;                                   // the contraction's route; the finish is one kernel for every shape
-    return fmmt_linear_wgrad_finish(dtype, M, N, K, dw, db, workspace, workspace_bytes, stream);
-}
-}  // namespace
 
 extern "C" int fmmt_linear_wgrad(int dtype, int M, int N, int K,
                                  const void* dy, int lddy, const void* x, int ldx,
                                  float* dw, float* db, const float* rowscale, int rows_per_scale, int x_epi,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    return linear_wgrad_impl(dtype, M, N, K, dy, lddy, x, ldx, dw, db, rowscale, rows_per_scale, x_epi, workspace, workspace_bytes, stream, nullptr);
+    if (!aligned16(dw)) return FMMT_EALIGN;
+    bool direct;
+    if (int rc = wgrad_contract(wgrad_query(GEMM_WGRAD, dtype, M, N, K, lddy, ldx, rowscale != nullptr, rows_per_scale, x_epi), dy, x, dw, db, db != nullptr,
+                                rowscale, workspace, workspace_bytes, stream, &direct)) return rc;
+    return direct ? 0 : fmmt_linear_wgrad_finish(dtype, M, N, K, dw, db, workspace, workspace_bytes, stream);
 }
 
 extern "C" int fmmt_linear_wgrad_route(int dtype, int M, int N, int K, int lddy, int ldx, int has_rowscale, int rows_per_scale, int x_epi, int mode) {
-    int route = 0, rc;
-    void* const pp = route_ptr(1);
-    const float* const rs = reinterpret_cast<const float*>(route_ptr(has_rowscale));
-    if (mode == 0)
-        rc = linear_wgrad_impl(dtype, M, N, K, pp, lddy, pp, ldx, reinterpret_cast<float*>(pp), reinterpret_cast<float*>(pp), rs, rows_per_scale, x_epi, pp, ~(size_t)0, nullptr, &route);
-    else if (mode == 1)
-        rc = linear_wgrad_partials_impl(dtype, M, N, K, pp, lddy, pp, ldx, 1, rs, rows_per_scale, x_epi, pp, ~(size_t)0, nullptr, &route);
-    else
-        return FMMT_EINVAL;
-    return rc ? rc : route;
+    if (mode != 0 && mode != 1) return FMMT_EINVAL;
+    return route_of(wgrad_query(mode == 0 ? GEMM_WGRAD : GEMM_WGRAD_PARTIALS, dtype, M, N, K, lddy, ldx, has_rowscale != 0, rows_per_scale, x_epi));
 }

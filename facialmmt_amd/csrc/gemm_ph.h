@@ -373,11 +373,10 @@ __global__ __launch_bounds__(512) void linear_nt_ph_kernel(LinArgs p) {
 }
 
 template <int EPI = 1, bool STAGGER = true, bool PRIO = true, int DBG = 0>
-int launch_ph(const LinArgs& a, hipStream_t st, int* route = nullptr, int grid = 256) {
+int launch_ph(const LinArgs& a, hipStream_t st, int grid = 256) {
     constexpr int lds = 2 * 4 * 128 * 128 + 8 * 16 * 144 + 8 * 512;   // ring + wave-private epilogue slabs + bias slots
     static FmmtLdsOnce lds_once;
-    if (a.N % 256 || a.K % 64 || a.K < 128) return FMMT_EINVAL;
-    if (route) { *route = FMMT_ROUTE_PH; return 0; }           // host-side route query (include/fmmt_route.h): name the kernel, launch nothing
+    if (a.N % 256 || a.K % 64 || a.K < 128) return FMMT_EINVAL;    // a probe's own shapes: ph_plan (gemm_plan.h) sends nothing here that this refuses
     if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_nt_ph_kernel<EPI, STAGGER, PRIO, DBG>), lds)) return rc_;
     LinArgs p = a;
     p.tiles_m = (a.M + 255) / 256;

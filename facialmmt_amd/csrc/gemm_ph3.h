@@ -447,17 +447,12 @@ __global__ __launch_bounds__(512) void linear_nt_ph3_kernel(LinArgs p) {
 }
 
 template <int EPI = 2, bool STAGGER = true, int WT = 2>
-int launch_ph3(const LinArgs& a, hipStream_t st, int* route = nullptr, int grid = 256) {
+int launch_ph3(const LinArgs& a, hipStream_t st, int grid = 256) {
     constexpr int BM = WT * 96, BN = (8 / WT) * 64;
     constexpr int lds = 2 * (BN + BM) * 128 + 8 * 16 * 144 + 8 * 512 + 8 * 1024;     // ring + wave-private epilogue slabs + bias slots + rowscale slots
     static_assert(lds <= 160 * 1024, "LDS");
     static FmmtLdsOnce lds_once;
-    if (a.N % BN || a.K % 64 || a.K < 128 || ((EPI == 4 || EPI == 5 || EPI == 6) && a.K < 192)) return FMMT_EINVAL;
-    if (route) {                                               // host-side route query (include/fmmt_route.h): name the kernel, launch nothing
-        *route = WT == 4 ? (EPI == 6 ? FMMT_ROUTE_PH3W_MUL_AUX : EPI == 5 ? FMMT_ROUTE_PH3W_OP : FMMT_ROUTE_PH3W_PLAIN)
-                         : (EPI == 6 ? FMMT_ROUTE_PH3_MUL_AUX : EPI == 5 ? FMMT_ROUTE_PH3_OP : EPI == 3 ? FMMT_ROUTE_PH3_GELU_PRE : FMMT_ROUTE_PH3_PLAIN);
-        return 0;
-    }
+    if (a.N % BN || a.K % 64 || a.K < 128 || ((EPI == 4 || EPI == 5 || EPI == 6) && a.K < 192)) return FMMT_EINVAL;     // a probe's own shapes: ph_plan (gemm_plan.h) sends nothing here that this refuses
     if (int rc_ = lds_once.set(reinterpret_cast<const void*>(&linear_nt_ph3_kernel<EPI, STAGGER, WT>), lds)) return rc_;
     LinArgs p = a;
     p.tiles_m = (a.M + BM - 1) / BM;

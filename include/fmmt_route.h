@@ -1,11 +1,12 @@
 /* libfmmt_hip -- which kernel family a GEMM launch takes, asked on the host (included by fmmt.h).
  *
  * fmmt_linear_fwd, fmmt_linear_fwd_seg3, fmmt_linear_fwd_splitk and fmmt_linear_wgrad / _partials choose among some fifty kernel
- * instantiations by shape, leading dimensions, epilogue and which optional operands are present.  The two queries below run the SAME
- * validation and dispatch code as those entry points -- one `int* route` threaded through it, filled in immediately before the place
- * where the launch would be issued -- and return the FMMT_ROUTE_* value of the kernel the launch would take, or the negative FMMT_E*
- * the entry point would return.  No launch, no HIP call, no device.  Pointer arguments are replaced by presence flags (0 / non-zero);
- * pointers count as 16-byte aligned and workspaces as large enough.
+ * instantiations by shape, leading dimensions, epilogue and which optional operands are present.  That choice is host arithmetic on
+ * the shape alone (csrc/gemm_plan.h: check_query() validates a call, plan_query() returns its plan), and the plan's route is the index an
+ * entry point takes into its table of launchers -- one entry per value below, nothing between planner and table changes a route.  The two
+ * queries below call the SAME two functions on the same query and return the plan's FMMT_ROUTE_* value, or the negative FMMT_E* the entry
+ * point would return.  No launch, no HIP call, no device.  Pointer arguments are replaced by presence flags (0 / non-zero); pointers count
+ * as 16-byte aligned and workspaces as large enough.
  *
  * Tests use them to prove that every kernel family is exercised with leading dimensions different from the row width
  * (tests/support_gemm_cases.py); callers may use them to see where a shape lands.

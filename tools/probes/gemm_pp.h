@@ -72,24 +72,11 @@ template <int I, int N, typename F> __device__ __forceinline__ void pp_for(F&& f
     }
 }
 
-// GELU of 8 values with PLAIN single-issue FMAs (one element per instruction): beside MFMAs a packed v_pk_fma_f32 costs ~12 cycles of matrix-pipe time each,
-// a plain v_fma_f32 ~0.5 (profiles/r05_issue_rates.txt) -- same polynomial, same coefficients as fmmt_common.h's packed form
+// GELU of 8 values: the form of fmmt_common.h that gemm_ph3.h's epilogue uses (one v_exp_f32 + plain single-issue FMAs; the clamped odd polynomial this probe
+// was measured with left the tree with its coefficient table)
 __device__ __forceinline__ void pp_gelu8(float (&v)[8]) {
-    constexpr int N = sizeof(fmmt_gelu_phi_poly) / sizeof(float);
-    constexpr float R = FMMT_GELU_PHI_R;
-    float xc[8], u[8], q[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) xc[j] = __builtin_amdgcn_fmed3f(v[j], -R, R);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) u[j] = __builtin_fmaf(xc[j] * xc[j], 2.0f / (R * R), -1.0f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = __builtin_fmaf(u[j], fmmt_gelu_phi_poly[N - 1], fmmt_gelu_phi_poly[N - 2]);
-#pragma unroll
-    for (int k = N - 3; k >= 0; --k)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) q[j] = __builtin_fmaf(q[j], u[j], fmmt_gelu_phi_poly[k]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = v[j] * __builtin_fmaf(q[j], xc[j], 0.5f);
+    for (int j = 0; j < 8; ++j) v[j] = gelu_exp_f(v[j]);
 }
 
 // EPI: 0 = no output (probe of the main loop alone), 1 = plain / bias, 2 = GELU with the pre-activation stored to y_pre (both tensors ld = ldy)
